@@ -22,6 +22,11 @@ N > 1 is STRONG scaling of the same workload (configs[3]): the reads are block-s
 ranks (contigs and their index replicated), candidate spanning reads are all-gathered, pile-ups
 are bin-packed over the ranks by n^2 L, cropped reads travel to the owners with one all-to-all(v)
 and the closed gaps are gathered (dentist_amd/parallel.py) -- bit-identical to the 1-GPU result.
+
+A plain run sets up, warms up, times --steps steps and prints the result line.  --full adds what
+takes time of its own: the two other operating points (fast_mode_timed, uncapped_partner_cut_timed),
+the CPU baseline and the consensus' edit distance to the truth.  --dump-outputs DIR writes the last
+timed step's results as .npy files (dump_outputs) so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -77,13 +82,15 @@ def kernel_traffic(args, world):
     return None, None, msg
 
 
-def closed_gap_stats(w, rec, bases):
+def closed_gap_stats(w, rec, bases, with_truth=True):
     """Gap bases closed (insertions that passed every gate) and, outside the timed region, their
-    edit distance to the truth."""
-    from dentist_amd import sim
-    from oracle import pyoracle as oz  # checker only, never timed
+    edit distance to the truth (with_truth; (None, None) without it)."""
     closed = rec[rec["status"] == 0]
     gap_bases = int((closed["ins_end"] - closed["ins_begin"]).sum())
+    if not with_truth:
+        return gap_bases, len(closed), None, None
+    from dentist_amd import sim
+    from oracle import pyoracle as oz  # checker only, never timed
     edits = truth_bases = 0
     for r in closed:
         g = int(r["contig_left"])
@@ -97,14 +104,72 @@ def closed_gap_stats(w, rec, bases):
     return gap_bases, len(closed), edits, truth_bases
 
 
+DUMP_SEED = 20261016     # fixed: the same sample of alignments in every run and every build
+DUMP_LAS = 150_000       # alignments sampled into las.npy
+DUMP_TRACES = 16_000     # of which the first ones have their trace values in trace.npy
+DUMP_BYTES = 64_000_000  # everything together
+
+
+def dump_outputs(path, run, world):
+    """What the timed path handed back in `run` (the last timed step), as .npy files under `path`, in an order that does
+    not depend on how the work was scheduled, so that two builds can be compared file for file:
+      las.npy        (n, 9) float64: a fixed seeded sample of the alignment records (rank 0's at N > 1), sorted by
+                     aread, bread, abpos, aepos, bbpos, bepos, flags, diffs, tlen (the columns, in that order)
+      trace.npy      float32: the trace values of the first sampled alignments, one after the other (tlen values each)
+      gaps.npy       (n, 17) float64: every pile-up's record (INSERTION_DTYPE without cons_off and pad), sorted by
+                     contig_left, contig_right, join
+      consensus.npy  float32: the consensus bases of those records in that order (cons_len each)
+      summary.npy    float64: alignments, trace values, the six filters' drop counts, pile-ups, pile-up entries, gap bases
+                     closed, world size"""
+    import dentist_amd
+    os.makedirs(path, exist_ok=True)
+    las, rec, bases = run["las"], run["rec"], run["bases"]
+    trace = run["trace"] if isinstance(run["trace"], np.ndarray) else run["trace"].numpy()
+    la_cols = ("aread", "bread", "abpos", "aepos", "bbpos", "bepos", "flags", "diffs", "tlen")
+    order = np.lexsort([las[f] for f in reversed(la_cols)])
+    if len(las) > DUMP_LAS:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(len(las), size=DUMP_LAS, replace=False))
+        order = order[pick]
+    sel = las[order]
+    rec_cols = [f for f in dentist_amd.INSERTION_DTYPE.names if f not in ("cons_off", "pad")]
+    rorder = np.lexsort([rec["join"], rec["contig_right"], rec["contig_left"]])
+    srec = rec[rorder]
+    cons = [bases[int(r["cons_off"]):int(r["cons_off"]) + int(r["cons_len"])] for r in srec]
+    out = {"las": np.stack([sel[f].astype(np.float64) for f in la_cols], axis=1).reshape(-1, len(la_cols)),
+           "gaps": np.stack([srec[f].astype(np.float64) for f in rec_cols], axis=1).reshape(-1, len(rec_cols)),
+           "consensus": (np.concatenate(cons) if cons else np.zeros(0, np.uint8)).astype(np.float32)}
+    closed = rec[rec["status"] == 0]
+    out["summary"] = np.array([len(las), len(trace), *run["info"]["filtered"], len(rec), run["info"].get("entries", -1),
+                               int((closed["ins_end"] - closed["ins_begin"]).sum()), world], dtype=np.float64)
+    # trace values: as many of the sampled alignments as fit in what the other files leave of the budget
+    room = (DUMP_BYTES - sum(a.nbytes for a in out.values())) // 4
+    tlen = sel["tlen"][:DUMP_TRACES].astype(np.int64)
+    nt = int(np.searchsorted(np.cumsum(tlen), room, side="right"))
+    if nt:
+        starts, lens = sel["toff"][:nt].astype(np.int64), tlen[:nt]
+        idx = np.repeat(starts - np.concatenate([[0], np.cumsum(lens)[:-1]]), lens) + np.arange(int(lens.sum()))
+        out["trace"] = trace[idx].astype(np.float32)
+    else:
+        out["trace"] = np.zeros(0, np.float32)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES, "dump_outputs: over the size budget"
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="cfg2_100Mb_1000gaps_1Mx15kb")
-    ap.add_argument("--cpu-seconds", type=float, default=40.0, help="CPU time budget of the cpu_baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the fast mode and the partner cut (--fast-steps, --ref-partners), run the CPU baseline "
+                         "(unless --no-cpu-baseline) and measure the consensus' edit distance to the truth; off by default: "
+                         "a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--cpu-seconds", type=float, default=40.0, help="CPU time budget of the cpu_baseline leg (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--kmer-mod", type=int, default=1,
                     help="modimer sampling of the mapping index: one canonical k-mer in kmer_mod is indexed / looked up.  "
                          "1 (default) = every k-mer, the reference's behaviour (damapper has no sampling, "
@@ -136,24 +201,35 @@ def main():
     ap.add_argument("--fast-steps", "--ref-steps", dest="fast_steps", type=int, default=3,
                     help="steps of the FAST MODE (modimers 1/8 in the mapping index, 60 reads per pile-up: two work-reducing "
                          "knobs the reference does not have) timed after the headline loop in the same process and reported "
-                         "as fast_mode_timed; 0 = skip; N = 1 only")
+                         "as fast_mode_timed; 0 = skip; N = 1 and --full only")
     ap.add_argument("--fast-kmer-mod", type=int, default=8)
     ap.add_argument("--fast-max-reads", type=int, default=60)
     ap.add_argument("--ref-partners", type=int, default=60,
                     help="partner reads per read of the pile-up all-vs-all in the third timed configuration (the headline's knobs "
-                         "plus dh_process_opts.max_partners = this): reported as uncapped_partner_cut_timed; 0 = skip")
+                         "plus dh_process_opts.max_partners = this): reported as uncapped_partner_cut_timed; 0 = skip; --full only")
     ap.add_argument("--max-partners", type=int, default=None, help="dh_process_opts.max_partners of the headline run (default 0: every pair)")
     ap.add_argument("--dev-share-gpu", action="store_true",
                     help="development only: all ranks on cuda:0 with gloo collectives (exercises the N > 1 "
                          "code path on a 1-GPU box; not a measurement)")
     args = ap.parse_args()
 
-    import torch
-    import torch.distributed as dist
+    from concurrent.futures import ThreadPoolExecutor
+    from dentist_amd import sim
+    from dentist_amd.parallel import shard_range
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    spec = WORKLOADS[args.workload]
+    # one workload for every N (strong scaling): the assembly on every rank, the reads block-sharded.  Host-only work
+    # (C++ without the GIL): it is generated while torch loads and the device comes up
+    lo, hi = shard_range(spec["nreads"], rank, world)
+    gen = ThreadPoolExecutor(max_workers=1)
+    workload = gen.submit(sim.Workload, seed=20260929, read_range=(lo, hi), **spec)
+
+    import torch
+    import torch.distributed as dist
+
     if world != args.gpus and world > 1:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     if not torch.cuda.is_available():
@@ -170,13 +246,10 @@ def main():
                                     device_id=torch.device("cuda", local_rank))
 
     import dentist_amd
-    from dentist_amd import sim
-    from dentist_amd.parallel import shard_range, sharded_process
+    from dentist_amd.parallel import sharded_process
 
-    spec = WORKLOADS[args.workload]
-    # one workload for every N (strong scaling): the assembly on every rank, the reads block-sharded
-    lo, hi = shard_range(spec["nreads"], rank, world)
-    w = sim.Workload(seed=20260929, read_range=(lo, hi), **spec)
+    w = workload.result()
+    gen.shutdown()
     stream = torch.cuda.current_stream().cuda_stream
     ctx = dentist_amd.Context(local_rank, stream=stream)
     A, B = ctx.db(w.contigs), ctx.db(w.reads)
@@ -237,8 +310,10 @@ def main():
         pst = dentist_amd.process_stats(ctx)
         cum = ctx.cum_stats().as_dict()  # every k_wave / k_seed launch of the step
         info["filtered"] = dropped.tolist()
-        return dict(las=las, rec=rec, bases=bases, ast=ast, pst=pst, cum=cum, info=info, mj=mj,
+        return dict(las=las, trace=trace, rec=rec, bases=bases, ast=ast, pst=pst, cum=cum, info=info, mj=mj,
                     t_map=t1 - t0, t_collect=t2 - t1, t_process=t3 - t2)
+
+    results = ("las", "trace", "rec", "bases")   # what a step hands back: only the last step's results are kept
 
     def barrier():
         torch.cuda.synchronize()
@@ -253,11 +328,13 @@ def main():
     runs = []
     for _ in range(args.steps):
         if runs:  # only the last step's results are inspected: the earlier buffers go back to the pools
-            for key in ("las", "rec", "bases"):  # before the next step allocates its own
+            for key in results:  # before the next step allocates its own
                 runs[-1].pop(key, None)
         runs.append(step())
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, runs[-1], world)
 
     # The headline loop above runs at the reference's behaviour by default (every k-mer looked up, every read of a pile-up
     # processed).  Two more operating points are timed here, inside the same run, the same way, and labelled as what they are:
@@ -271,16 +348,16 @@ def main():
         vruns = []
         for _ in range(nsteps):
             if vruns:
-                for key in ("las", "rec", "bases"):
+                for key in results:
                     vruns[-1].pop(key, None)
             vruns.append(step(vm, vp))
         barrier()
         return vruns, time.perf_counter() - t0_
 
     fast_runs, fast_dt, cut_runs, cut_dt = [], 0.0, [], 0.0
-    if args.fast_steps > 0 and world == 1:
+    if args.full and args.fast_steps > 0 and world == 1:
         for r in runs[:-1]:
-            for key in ("las", "rec", "bases"):
+            for key in results:
                 r.pop(key, None)
         if args.ref_partners > 0 and args.process_algo == 1 and not popts.max_partners:
             cpopts = dentist_amd.default_process_opts(algo=args.process_algo, **band_kw)
@@ -313,7 +390,8 @@ def main():
 
     if rank == 0:
         # the closed-gap records are the gathered result of all ranks (identical on every rank)
-        gap_all, nclosed_all, edits_all, truth_all = closed_gap_stats(w, last["rec"], last["bases"])
+        # (the edit distance of the consensus to the truth is a check of its own: --full)
+        gap_all, nclosed_all, edits_all, truth_all = closed_gap_stats(w, last["rec"], last["bases"], with_truth=args.full)
         ms_step = dt / args.steps * 1e3
         # extension kernels of the step (k_tile: mapping launches, pile-up all-vs-all, re-alignment, flanks; k_wave2 when
         # an algo is 0).  Algorithmic bytes of a launch = both sequences of every alignment it emits streamed once
@@ -460,7 +538,7 @@ def main():
             cut_runs, cut_dt, f"the headline's knobs with the pile-up all-vs-all bounded to {args.ref_partners} partner reads per "
             "read (dh_process_opts.max_partners; every read still votes in the consensus rounds) -- NOT the reference's "
             "behaviour: daligner aligns every pair of a pile-up (package.d:474-485)", args.kmer_mod) if cut_runs else None
-        if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(w, last, mopts, popts, args, gap_all, read_all)
         print(json.dumps(out))
     if world > 1:
