@@ -145,43 +145,11 @@ k_pack2_rc(const uint8_t *__restrict__ src, const int64_t *__restrict__ off, int
     }
 }
 
-// the same copy plane-packed, one thread per 32-base word (= one PlanePair); the words a sequence shares with its
-// neighbours are ORed in (the plane form is a permutation of the packed word's bits, so the parts combine the same way)
-__global__ void __launch_bounds__(256)
-k_pack2_rc_planes(const uint8_t *__restrict__ src, const int64_t *__restrict__ off, int32_t n, int64_t a0,
-                  unsigned long long *__restrict__ dst)
-{
-    const int32_t s = blockIdx.y;
-    if (s >= n) return;
-    const int64_t o = off[s], len = off[s + 1] - o;
-    if (len <= 0) return;
-    const int64_t w0 = (o - a0) >> 5, w1 = (o + len - 1 - a0) >> 5;  // first / last destination word
-    const int64_t sbase = 2 * o + len - 1;                           // source of base g is src[sbase - g]
-    for (int64_t w = w0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w <= w1; w += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t gw = a0 + (w << 5);
-        if (gw >= o && gw + 32 <= o + len) {
-            const uint8_t *A = src + (sbase - gw - 31);
-            uint64_t x0, x1, x2, x3;
-            __builtin_memcpy(&x0, A, 8);       // positions 31 .. 24
-            __builtin_memcpy(&x1, A + 8, 8);   // positions 23 .. 16
-            __builtin_memcpy(&x2, A + 16, 8);  // positions 15 .. 8
-            __builtin_memcpy(&x3, A + 24, 8);  // positions 7 .. 0
-            const uint64_t lo = pack8_rc(__builtin_bswap64(x3)) | (pack8_rc(__builtin_bswap64(x2)) << 16);
-            const uint64_t hi = pack8_rc(__builtin_bswap64(x1)) | (pack8_rc(__builtin_bswap64(x0)) << 16);
-            dst[w] = pk_to_planes(lo | (hi << 32));
-        } else {
-            const int64_t g0 = gw > o ? gw : o, g1 = gw + 32 < o + len ? gw + 32 : o + len;
-            uint64_t out = 0;
-            for (int64_t g = g0; g < g1; g++) out |= (uint64_t)((src[sbase - g] ^ 3u) & 3u) << (2 * (int)(g - gw));
-            atomicOr(&dst[w], (unsigned long long)pk_to_planes(out));
-        }
-    }
-}
 // the plane-packed reverse complements from the plane-packed FORWARD copy (made just before by k_pack2<true>) instead of
 // from the bytes again: 8 bytes read per 32 bases instead of 32 -- base g of the reverse complement of sequence s is the
 // complement of forward base sbase - g, so the 32 bases of a destination word are a run of 32 forward bases in reverse
 // order: two funnel shifts over two forward words per plane, a bit reversal, a complement.  Words shared with a
-// neighbouring sequence are ORed in, as in k_pack2_rc_planes.  fwd / dst: word 0 = base a0 (a multiple of 32), readable /
+// neighbouring sequence are ORed in, as in k_pack2_rc.  fwd / dst: word 0 = base a0 (a multiple of 32), readable /
 // zeroed PK_PAD bytes beyond both ends.
 __global__ void __launch_bounds__(256)
 k_planes_rc(const unsigned long long *__restrict__ fwd, const int64_t *__restrict__ off, int32_t n, int64_t a0,
@@ -664,10 +632,6 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
             if (slot < CAP) hits[slot] = ((uint64_t)strand << 63) | ((uint64_t)D << HIT_QBITS) | (uint32_t)qs;
         };
         auto flush = [&]() {
-#ifdef DH_SEED_NOLOAD
-            nq = 0;  // development: the rolling alone (no lookups), for the split of the lookup phase
-            return;
-#endif
             // the fat directory word of every queued k-mer: one 16-byte load, one memory round trip per flush
             ulonglong2 f[QN];
 #pragma unroll
@@ -1925,9 +1889,6 @@ __device__ void walk_chain(const DhNode *__restrict__ pool, int32_t head, int32_
     lo = best_k < 0 ? best_k : 0;
     hi = best_k > 0 ? best_k : 0;
     int32_t h = head;
-#ifdef DH_SKIP_WALK
-    return;
-#endif
     for (int32_t m = nb - 1; m >= 0 && h >= 0; m--) {
         const DhNode nd = pool[h];
         cd[m] = nd.d;
@@ -3440,20 +3401,8 @@ void dhk_pack2_rc(hipStream_t st, const uint8_t *src, const int64_t *off, int32_
     }
 }
 
-void dhk_pack2_rc_planes(hipStream_t st, const uint8_t *src, const int64_t *off, int32_t n, int32_t max_len, int64_t a0,
-                         uint8_t *dst)
-{
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_pack2_rc_bounds32, dim3((n + 255) / 256), dim3(256), 0, st, off, n, a0, (uint64_t *)dst);
-    int gx = (max_len / 32 + 255) / 256;
-    gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
-    for (int32_t s0 = 0; s0 < n; s0 += 65535) {
-        const int32_t cnt = n - s0 < 65535 ? n - s0 : 65535;
-        hipLaunchKernelGGL(k_pack2_rc_planes, dim3(gx, cnt), dim3(256), 0, st, src, off + s0, cnt, a0, (unsigned long long *)dst);
-    }
-}
-
-// the same result from the plane-packed forward copy `fwd` of the chunk (dhk_pack2_planes ran before on this stream)
+// the plane-packed reverse complements from the plane-packed forward copy `fwd` of the chunk (dhk_pack2_planes ran before on
+// this stream)
 void dhk_planes_rc(hipStream_t st, const uint8_t *fwd, const int64_t *off, int32_t n, int32_t max_len, int64_t a0, uint8_t *dst)
 {
     if (n <= 0) return;

@@ -9,7 +9,7 @@
 // canonical k-mer -- a contiguous slice of the directory and of a presence bitmap per bin --, then every bin is joined
 // with its slice held on chip:
 //
-//   k_mj_bitmap    (per index) one presence bit per bucket of a fine directory of A's keys (2^nbbits buckets, about 16 per
+//   k_mj_bitmap_part (per index) one presence bit per bucket of a fine directory of A's keys (2^nbbits buckets, about 16 per
 //                  indexed k-mer): the filter a partition's block keeps in LDS (2^(nbbits - 10) bits <= 128 KB).
 //   k_mj_part      one pass over the chunk's bases: a block takes a TILE of `tb` consecutive bases, rolls the canonical
 //                  k-mers of its positions (every lane starts from k - 1 bases packed with a few bit operations instead
@@ -83,7 +83,6 @@ struct MjView {
     int64_t rcap;
     int32_t npages;
     int32_t *status;
-    int32_t dbg;           // development switches (DH_MJ_DBG)
 };
 
 #ifdef __cplusplus

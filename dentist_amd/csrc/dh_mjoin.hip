@@ -62,7 +62,7 @@ __device__ __forceinline__ uint32_t mj_lanes_below(unsigned long long m)
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 // an entry of the stream (read once: the non-temporal hint keeps it from pushing the partition's directory slice out of
-// the XCD's L2, which the resolve sweep of k_mj_filter lives on)
+// the XCD's L2, which the resolve sweep of k_mj_filter2 lives on)
 __device__ __forceinline__ uint64_t mj_load8(const uint64_t *p) { return __builtin_nontemporal_load(p); }
 
 // exclusive prefix sum over the block's threads (one value each); *total = sum.  s_w: one word per wavefront.
@@ -103,21 +103,10 @@ __device__ __forceinline__ uint32_t mj_bit2(uint64_t rem, int sbits)
     const uint32_t x = (uint32_t)rem ^ (uint32_t)(rem >> 19) ^ ((uint32_t)(rem >> 32) << 13);
     return (x * 0x9E3779B1u) >> (32 - sbits);
 }
-__global__ void __launch_bounds__(256) k_mj_bitmap(const ulonglong2 *__restrict__ ent, int64_t n, int32_t k, int32_t nbbits, uint32_t *__restrict__ bm)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int remsh = 2 * k - MJ_PBITS, sbits = nbbits - MJ_PBITS;
-    const uint64_t key = ent[i].x & ~(1ull << 63);
-    const uint64_t p = key >> remsh, rem = key & ((1ull << remsh) - 1);
-    const uint64_t b1 = (p << sbits) | (rem >> (remsh - sbits)), b2 = (p << sbits) | mj_bit2(rem, sbits);
-    atomicOr(&bm[b1 >> 5], 1u << (b1 & 31));
-    atomicOr(&bm[b2 >> 5], 1u << (b2 & 31));
-}
 
-// The same bits without a global atomic (round 6): the entries of the index lie in bucket order, so the keys of a partition
-// are one contiguous range of `ent` -- a block finds it by binary search, sets the partition's slice of the bitmap in LDS and
-// writes it out.  (k_mj_bitmap: 2 x 10^8 scattered atomics at the chip's ~30 G/s = 6.7 ms of every index build.)
+// The bits without a global atomic: the entries of the index lie in bucket order, so the keys of a partition are one
+// contiguous range of `ent` -- a block finds it by binary search, sets the partition's slice of the bitmap in LDS and writes
+// it out.  (Scattered global atomics: 2 x 10^8 of them at the chip's ~30 G/s = 6.7 ms of every index build.)
 __global__ void __launch_bounds__(1024) k_mj_bitmap_part(const ulonglong2 *__restrict__ ent, int64_t n, int32_t k, int32_t nbbits, uint32_t *__restrict__ bm)
 {
     extern __shared__ uint32_t s_slice[];
@@ -444,232 +433,20 @@ __device__ __forceinline__ void mj_lookup(const IndexView &ix, const DhOpts &o, 
 
 // ------------------------------------------------------------------------------------ filter
 // A block keeps the bitmap slice of ONE partition in LDS (blocks pull (partition, slice of the tile groups) items, the
-// blocks of an XCD from the same queue).  A wavefront takes one TILE GROUP of the partition at a time: 16 segments, 16
-// lanes each (a segment holds 7 - 8 entries on average, so one coalesced load per lane covers it; longer segments take
-// further rounds), the entries of the groups behind it already in flight.  The entries that pass the filter -- the
-// k-mers of A among them, and 3 % of the others -- go, compacted, to the wavefront's page of the survivor pool, one range
-// per (group, partition): sseg[group][partition] = first << 24 | count.  No dependent global load: the kernel streams.
-__global__ void __launch_bounds__(MJ_PROBE_THREADS)
-k_mj_filter(IndexView ix, DhOpts o, MjView m)
-{
-    __shared__ uint32_t bm[1 << (MJ_MAXBITS - MJ_PBITS - 5)];
-    __shared__ int32_t s_item;
-    const int tid = threadIdx.x, lane = tid & (LANES - 1), wave = tid / LANES;
-    constexpr int NW = MJ_PROBE_THREADS / LANES;
-    constexpr int SPI = LANES / MJ_GROUP;          // segments per load instruction (4)
-    constexpr int NIT = MJ_GROUP / SPI;            // load instructions per group and round (4)
-    constexpr uint32_t SAFE = MJ_PAGE / 4;         // survivors one group may add to the wavefront's page
-    constexpr int DEPTH = 3;                       // groups in flight behind the one at hand
-    const int k = m.k, remsh = 2 * k - MJ_PBITS, sbits = m.nbbits - MJ_PBITS, bshift = remsh - sbits;
-    const uint64_t remmask = (1ull << remsh) - 1;
-    const int32_t slice_words = 1 << (sbits - 5);
-    const int32_t ng = m.ntiles_pad / MJ_GROUP;
-    const int32_t nitems_q = (MJ_P / 8) * MJ_SLICES;
-    const uint32_t xcc = mj_xcc_id();
-    const int sub = lane / MJ_GROUP, j = lane & (MJ_GROUP - 1);
-    uint64_t page_base = 0;
-    uint32_t fill = MJ_PAGE + 1;  // the wavefront has no page (yet, or the pool ran out)
-    uint64_t sweep_from = 0;  // survivors of this wavefront from here on are not resolved yet
-    bool pool_out = false;
-    int32_t curp = -1;
-    // RESOLVE: the survivors a wavefront has written for the partition at hand are looked up before it leaves the partition
-    // (and before it leaves a page) -- its XCD's L2 then holds the partition's 2 MB slice of the directory, because the
-    // XCD's blocks work on the same partition: 255 G lookups/s there against 54 G/s at random lines of HBM
-    // (scripts/join_probe.cpp).  A survivor becomes, in place: 0 = no hit; its only hit, strand << 63 | virtual A position <<
-    // 23 | position in the group + 1; or itself with bit 62 set = several hits (a palindrome, a repeat): k_mj_hits looks
-    // those up again.  Four lookups per lane in flight; nothing here is on the streaming loop's critical path.
-    auto resolve = [&](uint64_t from, uint64_t to, int32_t p) {
-        constexpr uint64_t ORI = 1ull << 63;
-        constexpr int RU = 4;
-        const uint64_t keytop = (uint64_t)p << remsh;
-        for (uint64_t i0 = from; i0 < to; i0 += RU * LANES) {
-            uint64_t sv[RU];
-            ulonglong2 f[RU];
-#pragma unroll
-            for (int u = 0; u < RU; u++) {
-                const uint64_t i = i0 + (uint64_t)u * LANES + lane;
-                sv[u] = i < to ? m.hits[i] : 0ull;
-            }
-#pragma unroll
-            for (int u = 0; u < RU; u++) {  // the directory words of all of them, together
-                f[u].x = DH_FAT_EMPTY;
-                f[u].y = 0;
-                if (sv[u]) f[u] = ix.fat[(uint32_t)((keytop | ((sv[u] >> MJ_REMSH) & remmask)) >> ix.shift)];
-            }
-#pragma unroll
-            for (int u = 0; u < RU; u++) {
-                const uint64_t i = i0 + (uint64_t)u * LANES + lane;
-                if (i >= to) continue;
-                const uint64_t key = keytop | ((sv[u] >> MJ_REMSH) & remmask);
-                const uint64_t bori = (sv[u] & MJ_ORI_BIT) ? ORI : 0ull;
-                const bool pal = (sv[u] & MJ_PAL_BIT) != 0;
-                const uint64_t posg1 = ((sv[u] >> MJ_PSH) & (uint64_t)(MJ_GROUP - 1)) * (uint64_t)m.tb + (sv[u] & ((1ull << MJ_POSBITS) - 1)) + 1;
-                uint64_t out = 0;
-                if (f[u].x != DH_FAT_EMPTY) {
-                    if ((f[u].x >> 62) != 1ull) {  // the bucket's only entry
-                        if ((f[u].x & ~ORI) == key && o.tcap >= 1) {
-                            const bool same = (f[u].x & ORI) == bori;
-                            const bool h0 = (same || pal) && (o.strands & 1), h1 = (!same || pal) && (o.strands & 2);
-                            if (h0 && h1)
-                                out = sv[u] | (1ull << 62);
-                            else if (h0 || h1)
-                                out = ((uint64_t)(h1 ? 1 : 0) << 63) | ((f[u].y & ((1ull << 39) - 1)) << 23) | posg1;
-                        }
-                    } else {  // several entries: counted with the full rules; one hit is taken from the walk
-                        uint32_t c = 0;
-                        uint64_t hh = 0;
-                        mj_lookup(ix, o, key, bori != 0, pal, [&](uint64_t v, int strand) {
-                            hh = ((uint64_t)strand << 63) | ((v & ((1ull << 39) - 1)) << 23) | posg1;
-                            c++;
-                        });
-                        out = c == 0 ? 0ull : (c == 1 ? hh : (sv[u] | (1ull << 62)));
-                    }
-                }
-                m.hits[i] = out;
-            }
-        }
-    };
-    for (int qq = 0; qq < 8; qq++) {
-        const uint32_t x = (xcc + qq) & 7u;  // own XCD's queue first, then whatever is left of the others'
-        for (;;) {
-            __syncthreads();
-            if (tid == 0) s_item = (int32_t)atomicAdd(&m.ctr[x], 1u);
-            __syncthreads();
-            const int32_t item = s_item;
-            if (item >= nitems_q) break;
-            const int32_t p = (int32_t)x + 8 * (item / MJ_SLICES), sl = item % MJ_SLICES;
-            if (p != curp) {
-                const uint4 *src = (const uint4 *)(m.bitmap + (int64_t)p * slice_words);
-                for (int i = tid; i < slice_words / 4; i += MJ_PROBE_THREADS) ((uint4 *)bm)[i] = src[i];
-                if (slice_words < 4 && tid < slice_words) bm[tid] = m.bitmap[(int64_t)p * slice_words + tid];
-                curp = p;
-                __syncthreads();
-            }
-            const int32_t g0 = (int32_t)((int64_t)ng * sl / MJ_SLICES), g1 = (int32_t)((int64_t)ng * (sl + 1) / MJ_SLICES);
-            const uint32_t *segp = m.seg + (int64_t)p * m.ntiles_pad;
-            // descriptors of group g (one per lane of a quarter) and, from them, the lane's entries of round 0
-            auto load_desc = [&](int32_t g) { return g < g1 ? segp[(int64_t)g * MJ_GROUP + j] : 0u; };
-            auto load_ent = [&](int32_t g, uint32_t sdv, uint64_t *e) {
-                bool more = false;
-#pragma unroll
-                for (int it = 0; it < NIT; it++) {
-                    const int sidx = it * SPI + sub;  // segment of the group this lane serves in load `it`
-                    const uint32_t sd = __shfl(sdv, sidx, LANES);
-                    const int32_t t = g * MJ_GROUP + sidx;
-                    const uint32_t cn = t < m.ntiles ? (sd & 0xFFFFu) : 0u;
-                    more = more || cn > (uint32_t)MJ_GROUP;
-                    e[it] = (uint32_t)j < cn ? mj_load8(m.ent + (int64_t)t * MJ_CAP + (sd >> 16) + j) : 0ull;  // (entries are never 0)
-                }
-                return more;
-            };
-            // pipeline: descriptors DEPTH + 1 groups ahead, entries DEPTH groups ahead
-            uint32_t sdv[DEPTH + 2];
-            uint64_t e[DEPTH + 1][NIT];
-            bool more[DEPTH + 1];
-            const int32_t gw = g0 + wave;
-#pragma unroll
-            for (int d = 0; d < DEPTH + 2; d++) sdv[d] = load_desc(gw + d * NW);
-#pragma unroll
-            for (int d = 0; d < DEPTH + 1; d++) {
-#pragma unroll
-                for (int it = 0; it < NIT; it++) e[d][it] = 0;
-                more[d] = false;
-                if (d < DEPTH && gw + d * NW < g1) more[d] = load_ent(gw + d * NW, sdv[d], e[d]);
-            }
-            for (int32_t g = gw; g < g1; g += NW) {
-                if (g + DEPTH * NW < g1) more[DEPTH] = load_ent(g + DEPTH * NW, sdv[DEPTH], e[DEPTH]);
-                const uint32_t sd_new = load_desc(g + (DEPTH + 2) * NW);
-                if (fill + SAFE > MJ_PAGE && !pool_out) {  // room for the group's survivors: they form one range
-                    if (fill <= MJ_PAGE && page_base + fill > sweep_from) resolve(sweep_from, page_base + fill, p);
-                    uint32_t pg = 0;
-                    if (lane == 0) pg = atomicAdd(&m.ctr[8], 1u);
-                    pg = __shfl(pg, 0, LANES);
-                    if (pg >= (uint32_t)m.npages) {
-                        // (the survivors that find no page are counted: the host sizes the pool by them and runs the chunk again)
-                        if (lane == 0) atomicOr(m.status, DH_ST_MJ_POOL);
-                        fill = MJ_PAGE + 1;
-                        pool_out = true;
-                    } else {
-                        page_base = (uint64_t)pg * MJ_PAGE;
-                        fill = 0;
-                    }
-                    sweep_from = page_base + fill;
-                }
-                const bool have_page = fill + SAFE <= MJ_PAGE;
-                const uint64_t first = page_base + fill;
-                uint32_t gtot = 0;
-                const bool any_more = __ballot(more[0]) != 0ull;
-                for (uint32_t rnd = 0;; rnd++) {
-                    bool again = false;
-                    if (rnd > 0) {  // (rare: a segment with more than 16 entries)
-#pragma unroll
-                        for (int it = 0; it < NIT; it++) {
-                            const int sidx = it * SPI + sub;
-                            const uint32_t sd = __shfl(sdv[0], sidx, LANES);
-                            const int32_t t = g * MJ_GROUP + sidx;
-                            const uint32_t cn = t < m.ntiles ? (sd & 0xFFFFu) : 0u, jj = rnd * MJ_GROUP + j;
-                            again = again || cn > (rnd + 1) * MJ_GROUP;
-                            e[0][it] = jj < cn ? mj_load8(m.ent + (int64_t)t * MJ_CAP + (sd >> 16) + jj) : 0ull;
-                        }
-                    } else
-                        again = more[0];
-                    // ---- the two bits of every entry; survivors compacted behind the group's earlier ones
-                    uint32_t before = 0;
-#pragma unroll
-                    for (int it = 0; it < NIT; it++) {
-                        const uint64_t ev = e[0][it];
-                        const uint64_t rem = (ev >> MJ_REMSH) & remmask;
-                        const uint32_t b1 = (uint32_t)(rem >> bshift);
-                        bool pass = ev != 0ull && ((bm[b1 >> 5] >> (b1 & 31)) & 1u);
-                        if (pass) {
-                            const uint32_t b2 = mj_bit2(rem, sbits);
-                            pass = (bm[b2 >> 5] >> (b2 & 31)) & 1u;
-                        }
-                        const unsigned long long bal = __ballot(pass);
-                        const uint32_t at = gtot + before + mj_lanes_below(bal);
-                        if (pass && have_page && at < SAFE)
-                            m.hits[first + at] = (ev & ~(0x3FFull << MJ_PSH)) | ((uint64_t)(it * SPI + sub) << MJ_PSH);
-                        before += (uint32_t)__popcll(bal);
-                    }
-                    gtot += before;
-                    if (!any_more || __ballot(again) == 0ull) break;
-                }
-                if (gtot > SAFE) {  // more survivors than a group may hold: a degenerate tile (one k-mer all over)
-                    if (lane == 0) atomicOr(m.status, DH_ST_MJ_OVERFLOW);
-                    gtot = 0;
-                }
-                if (lane == 0) m.hseg[(int64_t)g * MJ_P + p] = ((unsigned long long)first << 24) | (have_page ? gtot : 0u);
-                if (!have_page && gtot && lane == 0) atomicAdd((unsigned long long *)(m.ctr + 12), (unsigned long long)gtot);
-                if (have_page) fill += gtot;
-                // rotate the pipeline
-#pragma unroll
-                for (int d = 0; d < DEPTH; d++) {
-#pragma unroll
-                    for (int it = 0; it < NIT; it++) e[d][it] = e[d + 1][it];
-                    more[d] = more[d + 1];
-                }
-#pragma unroll
-                for (int d = 0; d < DEPTH + 1; d++) sdv[d] = sdv[d + 1];
-                sdv[DEPTH + 1] = sd_new;
-            }
-            if (fill <= MJ_PAGE && page_base + fill > sweep_from) {
-                resolve(sweep_from, page_base + fill, p);
-                sweep_from = page_base + fill;
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------ filter, flat lane mapping (round 6)
-// The filter above deals 16 lanes to every segment (tile, partition) -- 7-8 entries on average: half of the lanes idle in
-// every load, bit test, ballot and store, ~400 wave-instructions per 128 entries, the kernel VALU-bound at 62 ms per launch
-// unsampled (58 % VALU-busy SIMDs at 63 % lane use).  Here a wavefront takes 64 TILES of its partition at a time -- one
-// descriptor per lane, one coalesced load -- and maps the ~512 entries of their 64 segments FLAT onto its lanes: an
-// exclusive prefix sum of the counts (six DPP steps), a mark per segment start in a byte array of LDS, and for every round
-// of 64 consecutive entries the segment of a lane's entry is the running maximum of the marks (six more DPP steps and the
-// carry of the round before).  Every lane of a round tests an entry; ~55 wave-instructions per 64 entries.  The loads of
-// the first MJ_F2_R rounds are issued together before the first entry is tested.  Survivors, ranges, pages and the resolve
-// sweep are those of k_mj_filter: sseg[group][partition] still describes one range per group of 16 tiles.
+// blocks of an XCD from the same queue).  The entries that pass the filter -- the k-mers of A among them, and 3 % of the
+// others -- go, compacted, to the wavefront's page of the survivor pool (MJ_PAGE entries taken from the cursor ctr[8]; a
+// page is left only when the entries at hand might not fit, so pages fill to the brim), one range per (group of 16
+// tiles, partition): hseg[group][partition] = first survivor << 24 | count.  When the pool runs out, DH_ST_MJ_POOL is
+// raised and ctr[12] counts the survivors that found no page: the host sizes the pool by them and runs the chunk again.
+// The survivors a wavefront has written are resolved in place (the sweep below) before it leaves the partition or a page.
+// Lanes: a segment (tile, partition) holds 7-8 entries on average, so 16 lanes per segment would leave half of the lanes
+// idle in every load, bit test, ballot and store (~400 wave-instructions per 128 entries, VALU-bound at 62 ms per launch
+// unsampled).  A wavefront therefore takes 64 TILES of its partition at a time -- one descriptor per lane, one coalesced
+// load -- and maps the ~512 entries of their 64 segments FLAT onto its lanes: an exclusive prefix sum of the counts (six
+// DPP steps), a mark per segment start in a byte array of LDS, and for every round of 64 consecutive entries the segment
+// of a lane's entry is the running maximum of the marks (six more DPP steps and the carry of the round before).  Every
+// lane of a round tests an entry; ~55 wave-instructions per 64 entries.  The loads of the first MJ_F2_R rounds are issued
+// together before the first entry is tested.  No dependent global load on the streaming loop.
 #define MJ_F2_R 10          /* rounds whose loads are in flight together (640 entries; 512 expected) */
 #define MJ_F2_MARKS 1024    /* flat indices one pass over the marks covers */
 #define MJ_F2_TMAX 16383    /* entries of one partition in 64 tiles (14 bits of prefix; 512 expected -- repeat-rich reads put many
@@ -729,7 +506,12 @@ k_mj_filter2(IndexView ix, DhOpts o, MjView m)
     unsigned long long t_res_ = 0, t_bm_ = 0;
     const unsigned long long t_all_ = wall_clock64();
 #endif
-    // RESOLVE: as in k_mj_filter
+    // RESOLVE: the survivors a wavefront has written for the partition at hand are looked up before it leaves the partition
+    // (and before it leaves a page) -- its XCD's L2 then holds the partition's 2 MB slice of the directory, because the
+    // XCD's blocks work on the same partition: 255 G lookups/s there against 54 G/s at random lines of HBM
+    // (scripts/join_probe.cpp).  A survivor becomes, in place: 0 = no hit; its only hit, strand << 63 | virtual A position <<
+    // 23 | position in the group + 1; or itself with bit 62 set = several hits (a palindrome, a repeat): k_mj_hits looks
+    // those up again.  Four lookups per lane in flight; nothing here is on the streaming loop's critical path.
     auto resolve = [&](uint64_t from, uint64_t to, int32_t p) {
         constexpr uint64_t ORI = 1ull << 63;
         constexpr int RU = 4;
@@ -1182,11 +964,6 @@ extern "C" {
 void dhk_mj_bitmap(hipStream_t st, const ulonglong2 *ent, int64_t n, int32_t k, int32_t nbbits, uint32_t *bm)
 {
     if (n <= 0) return;
-    const char *ev = getenv("DH_MJ_BITMAP_ATOMICS");  // development / tests: the scattered global atomics of round 5
-    if (ev && atoi(ev) != 0) {
-        hipLaunchKernelGGL(k_mj_bitmap, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ent, n, k, nbbits, bm);
-        return;
-    }
     const size_t lds = sizeof(uint32_t) << (nbbits - MJ_PBITS - 5);  // (nbbits <= MJ_MAXBITS: 128 KB)
     if (lds > 65536) (void)hipFuncSetAttribute((const void *)k_mj_bitmap_part, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k_mj_bitmap_part, dim3(MJ_P), dim3(1024), lds, st, ent, n, k, nbbits, bm);
@@ -1215,10 +992,7 @@ void dhk_mj_run(hipStream_t st, DbView B, IndexView ix, DhOpts o, MjView m, int3
 #undef MJ_PART
     }
     hipLaunchKernelGGL(k_mj_transpose, dim3((unsigned)(m.ntiles_pad / 32)), dim3(256), 0, st, m);
-    if (m.dbg & 2)  // development / tests (DH_MJ_DBG=2): the filter of round 5, 16 lanes per segment
-        hipLaunchKernelGGL(k_mj_filter, dim3((unsigned)ncu), dim3(MJ_PROBE_THREADS), 0, st, ix, o, m);
-    else
-        hipLaunchKernelGGL(k_mj_filter2, dim3((unsigned)ncu), dim3(MJ_PROBE_THREADS), 0, st, ix, o, m);
+    hipLaunchKernelGGL(k_mj_filter2, dim3((unsigned)ncu), dim3(MJ_PROBE_THREADS), 0, st, ix, o, m);
     hipLaunchKernelGGL(k_mj_hits, dim3((unsigned)m.ngroups), dim3(MJ_THREADS), 0, st, B, ix, o, m);
 #ifdef DH_MJ_PROF
     if (getenv("DH_TRACE")) {

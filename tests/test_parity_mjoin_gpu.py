@@ -76,13 +76,13 @@ def test_the_tiers_of_the_seed_back_end(monkeypatch):
 
 
 def test_the_round_6_paths_against_their_switches(monkeypatch):
-    """Round 6: the filter of the join maps the entries of 64 tiles flat onto the lanes (k_mj_filter2; DH_MJ_DBG=2 = the filter
-    of round 5, 16 lanes per segment), the seed sort gives buckets above 256 hits a second counting pass over their own
-    diagonal range (DH_SEED_NO_REFINE=1 = the bitonic network as before) and a k_tile wavefront takes 64 work units per queue
-    atomic (DH_TILE_QBATCH=1 = one atomic per pass).  Unsampled reads of 12 kb on a 2 Mb assembly: ~700 true hits per read on
-    a few hundred neighbouring diagonals next to chance hits anywhere -- one slice of the read's diagonal range holds them
-    all, the case the second pass is for; reads spanning two contigs bring two such clusters.  Bit-exact against the oracle,
-    identical under every switch."""
+    """Round 6: the seed sort gives buckets above 256 hits a second counting pass over their own diagonal range
+    (DH_SEED_NO_REFINE=1 = the bitonic network as before), a k_tile wavefront takes 64 work units per queue atomic
+    (DH_TILE_QBATCH=1 = one atomic per pass), and the mapping join, whose filter maps the entries of 64 tiles flat onto the
+    lanes (k_mj_filter2), finds the hits of the directory lookups (DH_NO_MJOIN=1).  Unsampled reads of 12 kb on a 2 Mb
+    assembly: ~700 true hits per read on a few hundred neighbouring diagonals next to chance hits anywhere -- one slice of
+    the read's diagonal range holds them all, the case the second pass is for; reads spanning two contigs bring two such
+    clusters.  Bit-exact against the oracle, identical under every switch."""
     w = sim.Workload(2_000_000, 6, 500, 12000, seed=77, spacing=300_000)
     ctx = dentist_amd.Context(0)
     try:
@@ -92,17 +92,11 @@ def test_the_round_6_paths_against_their_switches(monkeypatch):
         assert ctx.align_stats().hits / w.reads.n > 400
         go = dentist_amd.default_align_opts(**kw)
         A, B = ctx.db(w.contigs), ctx.db(w.reads)
-        for env, val in (("DH_MJ_DBG", "2"), ("DH_SEED_NO_REFINE", "1"), ("DH_TILE_QBATCH", "1"), ("DH_NO_MJOIN", "1")):
+        for env, val in (("DH_SEED_NO_REFINE", "1"), ("DH_TILE_QBATCH", "1"), ("DH_NO_MJOIN", "1")):
             monkeypatch.setenv(env, val)
             other = ctx.align_db(A, B, go)
             monkeypatch.delenv(env)
             assert_same_las((las, trace), other)
-        # the presence bitmap of the index, made per partition in LDS (k_mj_bitmap_part) or by scattered global atomics as in
-        # round 5: it is made with the index of a DB, so a fresh DB object
-        monkeypatch.setenv("DH_MJ_BITMAP_ATOMICS", "1")
-        other = ctx.align_db(ctx.db(w.contigs), B, go)
-        monkeypatch.delenv("DH_MJ_BITMAP_ATOMICS")
-        assert_same_las((las, trace), other)
     finally:
         ctx.close()
 
@@ -211,7 +205,7 @@ def test_reads_with_low_complexity_tails_fill_one_partition(gpu_ctx, monkeypatch
     tiles a wavefront of k_mj_filter2 takes hold several thousand entries of that partition instead of ~512, so the flat
     lane mapping walks several windows of its segment marks (MJ_F2_MARKS = 1 024 flat indices each) and the segments are
     dozens of entries long.  The assembly holds poly-A stretches too (hits, the -t cap).  Bit-exact against the oracle, the
-    chunk stays with the join (no fall-back), identical to the round-5 filter and to the directory lookups."""
+    chunk stays with the join (no fall-back), identical to the directory lookups."""
     rng = np.random.default_rng(41)
     g = rng.integers(0, 4, 400_000).astype(np.uint8)
     for at in (50_000, 180_000, 310_000):
@@ -225,7 +219,7 @@ def test_reads_with_low_complexity_tails_fill_one_partition(gpu_ctx, monkeypatch
     assert chunks > 0 and fallbacks == 0
     go = dentist_amd.default_align_opts(**kw)
     A, B = gpu_ctx.db(contigs), gpu_ctx.db(reads)
-    for env, val in (("DH_MJ_DBG", "2"), ("DH_NO_MJOIN", "1")):
+    for env, val in (("DH_NO_MJOIN", "1"),):
         monkeypatch.setenv(env, val)
         other = gpu_ctx.align_db(A, B, go)
         monkeypatch.delenv(env)
