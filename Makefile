@@ -54,6 +54,10 @@ clean:
 tests/native/libdh_tile_host.so: tests/native/tile_host.cpp dentist_amd/csrc/dh_tile.h dentist_amd/csrc/dh_device.h
 	g++ -O2 -g -shared -fPIC -std=c++17 -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -Wno-unknown-pragmas -o $@ $<
 
+# k_tile's column loop on 32-bit words (dh_tile.h, dh_bitvec.h) against the 64-bit step: test infrastructure
+tests/native/libdh_bitvec_host.so: tests/native/bitvec_host.cpp dentist_amd/csrc/dh_tile.h dentist_amd/csrc/dh_bitvec.h dentist_amd/csrc/dh_device.h
+	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -Wno-unknown-pragmas -o $@ $<
+
 # the host thread pool (dentist_amd/csrc/dh_parallel.h) on its own: test infrastructure
 tests/native/libdh_pool_host.so: tests/native/pool_host.cpp dentist_amd/csrc/dh_parallel.h
 	g++ -O2 -g -shared -fPIC -std=c++17 -pthread -o $@ $<

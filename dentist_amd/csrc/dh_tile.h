@@ -16,6 +16,7 @@
 
 #include <stdint.h>
 
+#include "dh_bitvec.h"
 #include "dh_device.h"
 
 #if defined(__HIPCC__)
@@ -292,6 +293,181 @@ DH_HD void tile_col(TileT<WB> &t, typename BandVec<WB>::U p0, typename BandVec<W
     t.Pv = (V)(HN | (V)~(Xv | HP));
     t.Mv = (V)(HP & Xv);
     t.dbot += 1 - (int32_t)(D0 >> (WB - 1));
+}
+
+// The column step as k_tile runs it: the recurrence of tile_col on H = WB / 32 words of 32 bits (word h = rows
+// [32 h, 32 h + 32)), each three-input function one dhbv::b3 -- on gfx950 one v_bitop3_b32, which the compiler does not
+// form from 64-bit operations.  Exact Boolean identities of tile_col's expressions:
+//   Eq = (match & lv & dm) | wild, match = (p0 ^ n0) & (p1 ^ n1) with n0 / n1 = the COMPLEMENTED bits of the A base as masks;
+//   S = Eq & Pv and EM = Eq | Mv are formed from (match, wild) directly, D0 = ((S + Pv) ^ Pv) | EM,
+//   HP = Mv | ~(D0 | Pv), Pv' = (Pv & D0) | ~(Xv | HP), Mv' = HP & Xv with Xv = D0 >> 1 (across the words).
+// Template switches, each dropping work that is the identity where the caller uses it:
+//   LV   = false: lv is all ones (the columns past the first W/2 + 1; lv is then neither shifted nor applied);
+//   WILD = false: no row of the band is past the end of B' in this column or any earlier one of the tile (wild == 0 and
+//          z >= the columns to run: z and wild are left alone, the caller takes the columns off z afterwards);
+// and dbot is not counted per column: the top bit of D0 is shifted into dtop, and tile_dtop_flush adds a block's worth
+// (at most 32 columns) at once -- dbot += columns - popcount(dtop).
+template <int WB>
+struct TileH {
+    static constexpr int H = WB / 32;
+    uint32_t Pv[H], Mv[H], lv[H], wild[H], dm[H];
+    int32_t z;
+    uint32_t dtop;
+};
+
+template <int WB>
+DH_HD void tile_split(const TileT<WB> &t, TileH<WB> &s)
+{
+    for (int h = 0; h < TileH<WB>::H; h++) {
+        s.Pv[h] = (uint32_t)((uint64_t)t.Pv >> (32 * h));
+        s.Mv[h] = (uint32_t)((uint64_t)t.Mv >> (32 * h));
+        s.lv[h] = (uint32_t)((uint64_t)t.lv >> (32 * h));
+        s.wild[h] = (uint32_t)((uint64_t)t.wild >> (32 * h));
+        s.dm[h] = (uint32_t)((uint64_t)t.dm >> (32 * h));
+    }
+    s.z = t.z;
+    s.dtop = 0;
+}
+
+template <int WB>
+DH_HD void tile_join(const TileH<WB> &s, TileT<WB> &t)
+{
+    typedef typename BandVec<WB>::U V;
+    V Pv = 0, Mv = 0, lv = 0, wild = 0;
+    for (int h = 0; h < TileH<WB>::H; h++) {
+        Pv |= (V)((uint64_t)s.Pv[h] << (32 * h));
+        Mv |= (V)((uint64_t)s.Mv[h] << (32 * h));
+        lv |= (V)((uint64_t)s.lv[h] << (32 * h));
+        wild |= (V)((uint64_t)s.wild[h] << (32 * h));
+    }
+    t.Pv = Pv;
+    t.Mv = Mv;
+    t.lv = lv;
+    t.wild = wild;
+    t.z = s.z;
+}
+
+template <bool TAN, bool LV, bool WILD, int WB>
+DH_HD void tile_col_h(TileH<WB> &s, const uint32_t *p0, const uint32_t *p1, uint32_t n0, uint32_t n1)
+{
+    using namespace dhbv;
+    constexpr int H = TileH<WB>::H;
+    if (LV) {  // lv >>= 1 (arithmetic)
+        if (H == 2) s.lv[0] = funnel32(s.lv[1], s.lv[0], 1);
+        s.lv[H - 1] = (uint32_t)((int32_t)s.lv[H - 1] >> 1);
+    }
+    if (WILD) {  // wild >>= 1 (arithmetic), its top bit or'ed with z < 0
+        s.z -= 1;
+        if (H == 2) s.wild[0] = funnel32(s.wild[1], s.wild[0], 1);
+        s.wild[H - 1] = (uint32_t)((int32_t)s.wild[H - 1] >> 1) | ((uint32_t)s.z & 0x80000000u);
+    }
+    uint32_t S[H], EM[H];
+    for (int h = 0; h < H; h++) {
+        uint32_t a;
+        if (LV && TAN)
+            a = b3<(BA ^ BB) & BC>(p0[h], n0, s.lv[h] & s.dm[h]);
+        else if (LV)
+            a = b3<(BA ^ BB) & BC>(p0[h], n0, s.lv[h]);
+        else if (TAN)
+            a = b3<(BA ^ BB) & BC>(p0[h], n0, s.dm[h]);
+        else
+            a = p0[h] ^ n0;
+        const uint32_t e = b3<BA & (BB ^ BC)>(a, p1[h], n1);
+        if (WILD) {
+            S[h] = b3<(BA | BB) & BC>(e, s.wild[h], s.Pv[h]);
+            EM[h] = e | s.wild[h] | s.Mv[h];
+        } else {
+            S[h] = e & s.Pv[h];
+            EM[h] = e | s.Mv[h];
+        }
+    }
+    uint32_t sum[H];
+    if (H == 2) {  // the carry crosses the words
+        const uint64_t r = (((uint64_t)S[H - 1] << 32) | S[0]) + (((uint64_t)s.Pv[H - 1] << 32) | s.Pv[0]);
+        sum[0] = (uint32_t)r;
+        sum[H - 1] = (uint32_t)(r >> 32);
+    } else {
+        sum[0] = S[0] + s.Pv[0];
+    }
+    uint32_t D0[H], HP[H], HN[H], Xv[H];
+    for (int h = 0; h < H; h++) {
+        D0[h] = b3<(BA ^ BB) | BC>(sum[h], s.Pv[h], EM[h]);
+        HP[h] = b3<BA | ~(BB | BC)>(s.Mv[h], D0[h], s.Pv[h]);
+        HN[h] = s.Pv[h] & D0[h];
+    }
+    if (H == 2) Xv[0] = funnel32(D0[H - 1], D0[0], 1);
+    Xv[H - 1] = D0[H - 1] >> 1;
+    for (int h = 0; h < H; h++) {
+        s.Pv[h] = b3<BA | ~(BB | BC)>(HN[h], Xv[h], HP[h]);
+        s.Mv[h] = HP[h] & Xv[h];
+    }
+    s.dtop = funnel32(s.dtop, D0[H - 1], 31);  // (dtop << 1) | D0's top bit
+}
+
+// the end of a block of ncols <= 32 columns run by tile_col_h: their score changes of the bottom row into dbot
+template <int WB>
+DH_HD void tile_dtop_flush(TileH<WB> &s, int32_t &dbot, int32_t ncols)
+{
+    dbot += ncols - (int32_t)__builtin_popcount(s.dtop);
+    s.dtop = 0;
+}
+
+// The columns [sh0, sh1) of a block of 32 (column c = 32 blk + sh + 1) by tile_col_h, the bounds wave-uniform, so
+// that the loop runs under scalar control.  w = the block's plane words of B' (WB = 64: three per plane, 32: two), nab = the
+// COMPLEMENTED 2-bit packed A bases of the 16 columns the range lies in (bits 2 (sh & 15) .. +1: one v_bfe_i32 per bit gives
+// ~x0 / ~x1 as masks).  MASK: a lane runs column sh only if sh < lim (its tile ends inside the block); otherwise the
+// caller runs the loop under the lanes' `run` alone, and no compare or exec-mask round trip is issued per column.
+template <bool TAN, bool LV, bool WILD, bool MASK, int WB>
+DH_HD void tile_cols(TileH<WB> &s, const uint32_t (&w)[6], uint32_t nab, int32_t sh0, int32_t sh1, int32_t lim)
+{
+    constexpr int H = WB / 32;
+    for (int32_t sh = sh0; sh < sh1; sh++) {
+        if (!MASK || sh < lim) {
+            uint32_t p0[H], p1[H];
+            for (int h = 0; h < H; h++) {
+                p0[h] = dhbv::funnel32(w[h + 1], w[h], (uint32_t)sh);
+                p1[h] = dhbv::funnel32(w[3 + h + 1], w[3 + h], (uint32_t)sh);
+            }
+            const uint32_t o = (uint32_t)(2 * sh) & 31u;
+            tile_col_h<TAN, LV, WILD, WB>(s, p0, p1, dhbv::bitmask(nab, o), dhbv::bitmask(nab, o + 1u));
+        }
+    }
+}
+
+// One block of 32 columns, in its two halves of 16 (one word of A each): the columns every running lane has (sh < nfull) without
+// a per-lane test, then the rest [nfull, nsh) with it.  lim = the lane's columns left in the block (0 if it does not run).
+template <bool TAN, bool LV, bool WILD, int WB>
+DH_HD void tile_block_lw(TileH<WB> &s, const uint32_t (&w)[6], uint32_t nab0, uint32_t nab1, int32_t nfull, int32_t nsh, bool run,
+                         int32_t lim)
+{
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+        const int32_t h0 = 16 * half, h1 = nsh < h0 + 16 ? nsh : h0 + 16;
+        if (h0 >= h1) break;
+        const int32_t f = nfull < h0 ? h0 : (nfull > h1 ? h1 : nfull);
+        const uint32_t nab = half ? nab1 : nab0;
+        if (run) tile_cols<TAN, LV, WILD, false, WB>(s, w, nab, h0, f, 0);
+        tile_cols<TAN, LV, WILD, true, WB>(s, w, nab, f, h1, lim);
+    }
+}
+
+// a block by the wave-uniform switches of k_tile: the first block of a tile applies lv, `wild` = some running lane of the
+// wavefront reaches the end of B' in this tile
+template <bool TAN, int WB>
+DH_HD void tile_block(TileH<WB> &s, const uint32_t (&w)[6], uint32_t nab0, uint32_t nab1, bool first, bool wild, int32_t nfull,
+                      int32_t nsh, bool run, int32_t lim)
+{
+    if (first) {
+        if (wild)
+            tile_block_lw<TAN, true, true, WB>(s, w, nab0, nab1, nfull, nsh, run, lim);
+        else
+            tile_block_lw<TAN, true, false, WB>(s, w, nab0, nab1, nfull, nsh, run, lim);
+    } else {
+        if (wild)
+            tile_block_lw<TAN, false, true, WB>(s, w, nab0, nab1, nfull, nsh, run, lim);
+        else
+            tile_block_lw<TAN, false, false, WB>(s, w, nab0, nab1, nfull, nsh, run, lim);
+    }
 }
 
 // the columns of a tile in sequence (host; the device kernel runs the same steps in lock step)

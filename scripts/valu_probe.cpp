@@ -7,12 +7,14 @@
 // dependent-issue latency does not limit a single wave), and prints
 //     op, waves/SIMD, G wave-instr/s per SIMD, cycles per instruction at the measured shader clock.
 // Build and run on the GPU box:
-//     hipcc -O3 --offload-arch=gfx950 -o scripts/valu_probe scripts/valu_probe.cpp && scripts/valu_probe
+//     hipcc -O3 --offload-arch=gfx950 -o scripts/valu_probe scripts/valu_probe.cpp && scripts/valu_probe [name filter]
+// (e.g. `scripts/valu_probe v_` for all, `scripts/valu_probe or3` for v_or3_b32 only)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #define CHK(x)                                                                 \
@@ -70,6 +72,7 @@
 #define T_MINU(i) "v_min_u32 %" #i ", %" #i ", %8\n"
 #define T_MED3(i) "v_med3_i32 %" #i ", %" #i ", %8, %9\n"
 #define T_SAD(i) "v_sad_u32 %" #i ", %" #i ", %8, %9\n"
+#define T_BITOP3(i) "v_bitop3_b32 %" #i ", %" #i ", %8, %9 bitop3:0x96\n"
 // 64-bit
 #define T_ADD64(i) "v_add_co_u32 %L" #i ", vcc, %L" #i ", %8\nv_addc_co_u32 %H" #i ", vcc, %H" #i ", %9, vcc\n"
 #define T_LSHR64(i) "v_lshrrev_b64 %" #i ", 1, %" #i "\n"
@@ -79,14 +82,14 @@
 enum {
     K_ADD, K_AND, K_XOR, K_LSHL, K_ALIGNBIT, K_BFI, K_OR3, K_ANDOR, K_ADD3, K_LSHLADD, K_MAX, K_CNDMASK, K_BCNT,
     K_FFBL, K_NOT, K_XNOR, K_DPP, K_DPPROW, K_ADDDPP, K_CMP, K_MULLO, K_MUL24, K_PERM, K_BPERM, K_SUBREV, K_MINU,
-    K_MED3, K_SAD, K_PKADD, K_LSHR64, K_LSHL64, K_N
+    K_MED3, K_SAD, K_PKADD, K_LSHR64, K_LSHL64, K_BITOP3, K_N
 };
 static const char *names[K_N] = {
     "v_add_u32", "v_and_b32", "v_xor_b32", "v_lshlrev_b32", "v_alignbit_b32", "v_bfi_b32", "v_or3_b32", "v_and_or_b32",
     "v_add3_u32", "v_lshl_add_u32", "v_max_i32", "v_cndmask_b32", "v_bcnt_u32_b32", "v_ffbl_b32", "v_not_b32",
     "v_xnor_b32", "v_mov_dpp quad_perm", "v_mov_dpp row_shr", "v_add_u32_dpp row_shr", "v_cmp_lt_i32", "v_mul_lo_u32",
     "v_mul_u32_u24", "v_perm_b32", "ds_bpermute_b32", "v_subrev_u32", "v_min_u32", "v_med3_i32", "v_sad_u32",
-    "v_pk_add_u16", "v_lshrrev_b64", "v_lshlrev_b64"};
+    "v_pk_add_u16", "v_lshrrev_b64", "v_lshlrev_b64", "v_bitop3_b32"};
 
 template <int K>
 __global__ void __launch_bounds__(64) k_probe(uint32_t *out, uint32_t seed, unsigned long long *clk)
@@ -132,6 +135,7 @@ __global__ void __launch_bounds__(64) k_probe(uint32_t *out, uint32_t seed, unsi
             if (K == K_MED3) OP8(T_MED3);
             if (K == K_SAD) OP8(T_SAD);
             if (K == K_PKADD) OP8(T_PKADD);
+            if (K == K_BITOP3) OP8(T_BITOP3);
             if (K == K_BPERM) {
                 OP8(T_BPERM);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -149,8 +153,9 @@ __global__ void __launch_bounds__(64) k_probe(uint32_t *out, uint32_t seed, unsi
 }
 
 template <int K>
-static void run(int ncu, uint32_t *d_out, unsigned long long *d_clk)
+static void run(int ncu, uint32_t *d_out, unsigned long long *d_clk, const char *only)
 {
+    if (only && !strstr(names[K], only)) return;
     for (int wps = 1; wps <= 8; wps++) {
         if (wps == 7) continue;
         const int grid = ncu * 4 * wps;  // one 64-thread block = one wave; 4 SIMDs per CU
@@ -179,14 +184,15 @@ static void run(int ncu, uint32_t *d_out, unsigned long long *d_clk)
 }
 
 template <int K>
-static void run_all(int ncu, uint32_t *d_out, unsigned long long *d_clk)
+static void run_all(int ncu, uint32_t *d_out, unsigned long long *d_clk, const char *only)
 {
-    run<K>(ncu, d_out, d_clk);
-    if constexpr (K + 1 < K_N) run_all<K + 1>(ncu, d_out, d_clk);
+    run<K>(ncu, d_out, d_clk, only);
+    if constexpr (K + 1 < K_N) run_all<K + 1>(ncu, d_out, d_clk, only);
 }
 
-int main()
+int main(int argc, char **argv)
 {
+    const char *only = argc > 1 ? argv[1] : nullptr;  // optional: only the op classes whose name contains this
     hipDeviceProp_t p;
     CHK(hipGetDeviceProperties(&p, 0));
     const int ncu = p.multiProcessorCount;
@@ -195,6 +201,6 @@ int main()
     unsigned long long *d_clk;
     CHK(hipMalloc(&d_out, (size_t)ncu * 4 * 8 * 64 * 4));
     CHK(hipMalloc(&d_clk, 8));
-    run_all<0>(ncu, d_out, d_clk);
+    run_all<0>(ncu, d_out, d_clk, only);
     return 0;
 }
