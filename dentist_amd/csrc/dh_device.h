@@ -1,4 +1,5 @@
-// dh_device.h -- POD views shared by the kernels (dh_kernels.hip) and the host side (dh_api.cpp).
+// dh_device.h -- POD views shared by the kernels (dh_kernels.hip, dh_seed.hip, dh_wave.hip) and the host side (dh_api.cpp), and the launchers
+// (dhk_*) of those three files.
 #ifndef DH_DEVICE_H
 #define DH_DEVICE_H
 

@@ -18,7 +18,7 @@
 //                 B side walks its chain: equal k-mers of the same orientation are forward-strand hits, of the
 //                 opposite orientation reverse-strand hits (palindromes both) -- exactly the hits the directory
 //                 lookups produce (same -t cap per orientation class, same self / symmetric-pair rules,
-//                 dh_kernels.hip seed_item::emit).  Hits are counted per B read, a contiguous range of the hit
+//                 dh_seed.hip seed_item::emit).  Hits are counted per B read, a contiguous range of the hit
 //                 buffer is reserved with ONE device-scope atomic per block, and the hits are written grouped by
 //                 B read; segtab[segrow[read] + slice] = (first hit, count).
 //   k_seed<.., JOIN>  the seed filter's back end unchanged (sort by (strand, diagonal, position), band coverage,

@@ -1,4 +1,4 @@
-// dh_kmer.h -- device helpers shared by the seed kernels (dh_kernels.hip) and the pile-up k-mer join (dh_join.hip):
+// dh_kmer.h -- device helpers shared by the seed kernel (dh_seed.hip), the index build (dh_kernels.hip) and the k-mer joins (dh_join.hip, dh_mjoin.hip):
 // modimer sampling on canonical k-mers, unaligned 8-byte loads, soft-mask test of a k-mer.
 #ifndef DH_KMER_H
 #define DH_KMER_H

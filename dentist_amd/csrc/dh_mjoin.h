@@ -2,7 +2,7 @@
 // source/dentist/dazzler.d:6158-6170, one call per read block: snakemake/Snakefile:1143-1170) as a radix-partitioned
 // k-mer join instead of one random directory line per looked-up k-mer.
 //
-// The generic seed filter (k_seed, dh_kernels.hip) asks the fat directory of A for every sampled k-mer of a read: a
+// The generic seed filter (k_seed, dh_seed.hip) asks the fat directory of A for every sampled k-mer of a read: a
 // random 64-byte line each, of which 16 bytes are used and 94 % find nothing (13 % error: 0.87^20 intact 20-mers).  The
 // part's random-line rate (55 G lines/s, scripts/rand_access_probe.cpp) bounds it: 2 x 28.6 ms per step at 1/8
 // sampling, 458 ms without sampling.  Here the k-mers of the reads are first binned by the top MJ_PBITS bits of their

@@ -1,6 +1,6 @@
 // dh_mjoin.hip -- gfx950 kernels of the radix-partitioned k-mer join that seeds a mapping pass (design: dh_mjoin.h).
 // Replaces, for `damapper ref reads.block` (source/dentist/dazzler.d:6158-6170), the directory lookups of the seed filter
-// (k_seed, dh_kernels.hip): the hits a read gets are the same multiset.
+// (k_seed, dh_seed.hip): the hits a read gets are the same multiset.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -386,7 +386,7 @@ k_mj_transpose(MjView m)
     }
 }
 
-// the lookup of one k-mer with the rules of seed_item's flush() (dh_kernels.hip): the bucket's only entry from the fat
+// the lookup of one k-mer with the rules of seed_item's flush() (dh_seed.hip): the bucket's only entry from the fat
 // directory word, or the walk of a bucket with the -t cap per orientation class; strands as o.strands allows
 namespace {
 template <typename F>
@@ -773,7 +773,7 @@ k_mj_filter2(IndexView ix, DhOpts o, MjView m)
 
 // ------------------------------------------------------------------------------------ hits, by read
 // A block per tile group: the survivors of the group's 1024 (partition) lists are looked up in the fat directory with
-// exactly the rules of seed_item's flush() (dh_kernels.hip: the bucket's only entry from the directory word, or the walk
+// exactly the rules of seed_item's flush() (dh_seed.hip: the bucket's only entry from the directory word, or the walk
 // of a bucket with the -t cap per orientation class), the hits are counted per read, the group's range of rhits is
 // reserved, and a second pass over the survivors that had hits writes them, finished -- strand << 63 | diagonal << 24 |
 // position on the oriented read: the hit encoding of k_seed --, grouped by read.  No buffer bounds the hits of a group.
