@@ -8,7 +8,8 @@ import pytest
 
 import dentist_amd
 from dentist_amd import sim
-from helpers import plant_long_indels, plant_gap_insertions, assert_same_las
+from helpers import (plant_long_indels, plant_gap_insertions, assert_same_las, la_chains, oracle_gap_entries, batch_order,
+                     cap_entries)
 from oracle import process as pr
 from oracle import pyoracle as oz
 
@@ -374,24 +375,9 @@ def test_pile_ups_of_the_graph_builder_with_extension_entries(gpu_ctx, algo, max
     piles, skipped = dentist_amd.scaffold_spanning_pileups(las, w.contigs.off, w.reads.off, gaps_in, with_extensions=True,
                                                            min_spanning_reads=po.min_reads)
     # ---- membership against the oracle's builder
-    chains = [sc.chain(i, int(l["aread"]) + 1, w.contigs.length(int(l["aread"])), int(l["bread"]) + 1,
-                       w.reads.length(int(l["bread"])), bool(l["flags"] & 1), int(l["abpos"]), int(l["aepos"]),
-                       int(l["bbpos"]), int(l["bepos"]), disabled=bool(l["flags"] & 0x20)) for i, l in enumerate(las)]
-    exp = {}
-    for e, ras in sc.build(w.contigs.n, chains, [(int(a) + 1, int(b) + 1) for a, b in gaps_in], min_spanning_reads=po.min_reads):
-        (c0, p0), (c1, p1) = e["start"], e["end"]
-        if not (p0 == sc.END and p1 == sc.BEGIN and c1 == c0 + 1):
-            continue
-        ent = []
-        for ra in ras:
-            if len(ra) == 2:
-                a, b = sorted(ra, key=lambda s: s[0]["a_id"])
-                ent.append((a[0]["b_id"] - 1, a[0]["id"], b[0]["id"]))
-            elif ra[0][0]["a_id"] == c0:
-                ent.append((ra[0][0]["b_id"] - 1, ra[0][0]["id"], -1))
-            else:
-                ent.append((ra[0][0]["b_id"] - 1, -1, ra[0][0]["id"]))
-        exp[c0 - 1] = sorted(ent, key=lambda t: t[0])   # stable: by read, then the builder's order
+    built = sc.build(w.contigs.n, la_chains(las, w.contigs, w.reads), [(int(a) + 1, int(b) + 1) for a, b in gaps_in],
+                     min_spanning_reads=po.min_reads)
+    exp = {g: sorted(ent, key=lambda t: t[0]) for g, ent in oracle_gap_entries(built).items()}   # stable: by read, then the builder's order
     got = {}
     for i in range(len(piles)):
         g, tri = piles.get(i)
@@ -451,43 +437,10 @@ def test_the_benched_chain_against_the_oracle(gpu_ctx):
     gp, _ = dentist_amd.scaffold_spanning_pileups(las, w.contigs.off, w.reads.off, gaps_in, with_extensions=True,
                                                   min_spanning_reads=po.min_reads)
     piles = gp.select(las, po)
-    chains = [sc.chain(i, int(l["aread"]) + 1, w.contigs.length(int(l["aread"])), int(l["bread"]) + 1,
-                       w.reads.length(int(l["bread"])), bool(l["flags"] & 1), int(l["abpos"]), int(l["aepos"]),
-                       int(l["bbpos"]), int(l["bepos"]), disabled=bool(l["flags"] & 0x20)) for i, l in enumerate(flas)]
-    exp = {}
-    for e, ras in sc.build(w.contigs.n, chains, [(int(a) + 1, int(b) + 1) for a, b in gaps_in], min_spanning_reads=po.min_reads):
-        (c0, p0), (c1, p1) = e["start"], e["end"]
-        if not (p0 == sc.END and p1 == sc.BEGIN and c1 == c0 + 1):
-            continue
-        ent = []
-        for ra in ras:
-            if len(ra) == 2:
-                a, b = sorted(ra, key=lambda s_: s_[0]["a_id"])
-                ent.append((a[0]["b_id"] - 1, a[0]["id"], b[0]["id"]))
-            elif ra[0][0]["a_id"] == c0:
-                ent.append((ra[0][0]["b_id"] - 1, ra[0][0]["id"], -1))
-            else:
-                ent.append((ra[0][0]["b_id"] - 1, -1, ra[0][0]["id"]))
-        ent.sort(key=lambda t: (t[0], t[1] < 0))   # read order; the halves of a spanning read that opens with an extension: left one first
-        if len(ent) > po.max_reads:   # the cap: distinct reads first, then the lowest error rate of the anchoring alignments
-            def err(t):
-                ln = sum(int(flas[i]["aepos"] - flas[i]["abpos"]) for i in t[1:] if i >= 0)
-                df = sum(int(flas[i]["diffs"]) for i in t[1:] if i >= 0)
-                return df * 1000000 // max(ln, 1)
-            second = [False] * len(ent)   # every entry of a read but its best one ranks behind all first entries
-            x0 = 0
-            while x0 < len(ent):
-                x1 = x0
-                while x1 < len(ent) and ent[x1][0] == ent[x0][0]:
-                    x1 += 1
-                best = min(range(x0, x1), key=lambda x: (err(ent[x]), x))
-                for x in range(x0, x1):
-                    second[x] = x != best
-                x0 = x1
-            ext = [t[1] < 0 or t[2] < 0 for t in ent]   # ... and extension entries behind the reads that span the gap
-            order = sorted(range(len(ent)), key=lambda x: (2 * ext[x] + second[x], err(ent[x]), x))[:po.max_reads]
-            ent = [ent[x] for x in sorted(order)]
-        exp[c0 - 1] = ent
+    built = sc.build(w.contigs.n, la_chains(flas, w.contigs, w.reads), [(int(a) + 1, int(b) + 1) for a, b in gaps_in],
+                     min_spanning_reads=po.min_reads)
+    # read order, then the cap: distinct reads first, then the lowest error rate of the anchoring alignments (helpers.py)
+    exp = {g: cap_entries(batch_order(ent), flas, po.max_reads) for g, ent in oracle_gap_entries(built).items()}
     got = {}
     for i in range(len(piles)):
         g, tri = piles.get(i)
