@@ -95,6 +95,9 @@ SYMBOLS = [
     "dh_shard_unpack_cropped", "dh_insertions_read_ids", "dh_insertions_read_ids_off", "dh_output_assembly", "dh_default_output_opts",
     "dh_common_trace_point", "dh_pileups_create_joins", "dh_pileups_get_join", "dh_scaffold_all_pileups",
     "dh_crop_pileups_masked", "dh_process_pileups_masked", "dh_process_pileups_set", "dh_la_set_trace_on_device", "dh_scaffold_graph_probe",
+    "dh_la_edit_paths", "dh_la_set_edit_paths", "dh_edit_paths_destroy", "dh_edit_paths_count", "dh_edit_paths_op_off",
+    "dh_edit_paths_ops", "dh_edit_paths_score", "dh_edit_paths_tile_off", "dh_edit_paths_tile_score",
+    "dh_edit_paths_general_tiles", "dh_format_cigar", "dh_format_alignment",
 ]
 
 _LIB = None
@@ -204,6 +207,21 @@ def lib():
     L.dh_output_fasta.argtypes = [ctypes.c_char_p, ctypes.c_char_p, vp, vp, i32, vp, ctypes.POINTER(ctypes.c_char_p),
                                   vp, vp, i32, vp, i32, i32]
     L.dh_dazz_header.restype = ctypes.c_char_p
+    L.dh_la_edit_paths.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, i64, ctypes.POINTER(vp)]
+    L.dh_la_set_edit_paths.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.POINTER(vp)]
+    L.dh_edit_paths_destroy.argtypes = [vp]
+    L.dh_edit_paths_destroy.restype = None
+    for fn in (L.dh_edit_paths_count, L.dh_edit_paths_general_tiles):
+        fn.argtypes = [vp]
+        fn.restype = i64
+    for fn in (L.dh_edit_paths_op_off, L.dh_edit_paths_ops, L.dh_edit_paths_score, L.dh_edit_paths_tile_off,
+               L.dh_edit_paths_tile_score):
+        fn.argtypes = [vp]
+        fn.restype = vp
+    L.dh_format_cigar.argtypes = [vp, i64, i32, vp, i64]
+    L.dh_format_cigar.restype = i64
+    L.dh_format_alignment.argtypes = [vp, vp, vp, i64, i32, vp, i64]
+    L.dh_format_alignment.restype = i64
     _LIB = L
     return L
 
@@ -353,6 +371,24 @@ class Context:
         fetches what the cropper reads; .numpy() downloads everything)."""
         return _map_reads(self, A, B, opts, popts, first, count, repeat_mask, sorted, candidates, trace_on_device)
 
+    def edit_paths(self, A, B, las, trace=None, tspace=None, first=0, count=None):
+        """dh_la_edit_paths: the base-level alignment of records [first, first + count) from their trace points, as an
+        EditPaths.  `las` may be a raw handle of align_db_block(..., raw=True) (dh_la_set_edit_paths; trace and tspace are
+        the set's own)."""
+        h = ctypes.c_void_p()
+        L = lib()
+        if isinstance(las, ctypes.c_void_p):
+            n = L.dh_la_set_count(las)
+            count = n - first if count is None else count
+            _check(L.dh_la_set_edit_paths(self._h, A._h, B._h, las, int(first), int(count), ctypes.byref(h)))
+        else:
+            arr = np.ascontiguousarray(las, dtype=LA_DTYPE)
+            tr = np.ascontiguousarray(trace, dtype=np.uint16)
+            count = len(arr) - first if count is None else count
+            _check(L.dh_la_edit_paths(self._h, A._h, B._h, arr.ctypes.data, len(arr), tr.ctypes.data, int(tspace), int(first),
+                                      int(count), ctypes.byref(h)))
+        return EditPaths(h)
+
     def align_db_block(self, A, B, first, count, opts, select_best=False, raw=False):
         """`damapper ref reads.<block>`: reads [first, first + count) of B against A.  raw=True
         returns the library handle (for merge_las) instead of numpy views."""
@@ -363,6 +399,71 @@ class Context:
             return h
         las, trace, _ = _take_la_set(h)
         return las, trace
+
+
+class EditPaths:
+    """Result of Context.edit_paths: numpy views of a library-owned dh_edit_paths (alive as long as this object is).
+    ops: one byte per op (0 match, 1 deletion, 2 insertion, 3 mismatch), record i at ops[op_off[i]:op_off[i + 1]];
+    score: per record; tile_score[tile_off[i]:tile_off[i + 1]]: per trace tile of record i; general_tiles: tiles
+    aligned by the full-matrix kernel."""
+
+    def __init__(self, h):
+        L = lib()
+        self._h = h
+        n = L.dh_edit_paths_count(h)
+
+        def view(ptr, ctype, count, dtype):
+            if not count:
+                return np.zeros(0, dtype=dtype)
+            buf = (ctype * count).from_address(ptr)
+            buf._owner = self
+            return np.frombuffer(buf, dtype=dtype)
+        self.op_off = view(L.dh_edit_paths_op_off(h), ctypes.c_int64, n + 1, np.int64)
+        self.tile_off = view(L.dh_edit_paths_tile_off(h), ctypes.c_int64, n + 1, np.int64)
+        self.score = view(L.dh_edit_paths_score(h), ctypes.c_int32, n, np.int32)
+        self.ops = view(L.dh_edit_paths_ops(h), ctypes.c_uint8, int(self.op_off[-1]), np.uint8)
+        self.tile_score = view(L.dh_edit_paths_tile_score(h), ctypes.c_uint16, int(self.tile_off[-1]), np.uint16)
+        self.general_tiles = int(L.dh_edit_paths_general_tiles(h))
+
+    def __len__(self):
+        return len(self.score)
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().dh_edit_paths_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def _format(fn, *args):
+    n = fn(*args, None, 0)
+    if n < 0:
+        _check(int(n))
+    buf = ctypes.create_string_buffer(int(n) + 1)
+    assert fn(*args, buf, int(n) + 1) == n
+    return buf.value.decode()
+
+
+def format_cigar(ops, extended=True):
+    """dh_format_cigar: runs of = X I D (extended) or M I D of an op array of Context.edit_paths."""
+    o = np.ascontiguousarray(ops, dtype=np.uint8)
+    return _format(lib().dh_format_cigar, o.ctypes.data, len(o), int(bool(extended)))
+
+
+def _seq_bytes(x):
+    return np.frombuffer(x.encode(), dtype=np.uint8) if isinstance(x, str) else np.ascontiguousarray(x, dtype=np.uint8)
+
+
+def format_alignment(a, b, ops, width=0):
+    """dh_format_alignment: the reference's SequenceAlignment.toString(width) of sequences a (A side) and b (B side, in the
+    frame of the alignment) under an op array; a / b are strings or base-code arrays."""
+    o = np.ascontiguousarray(ops, dtype=np.uint8)
+    sa, sb = _seq_bytes(a), _seq_bytes(b)
+    if int(np.count_nonzero(o != 2)) > len(sa) or int(np.count_nonzero(o != 1)) > len(sb):
+        raise ValueError("the ops consume more bases than the sequences have")
+    return _format(lib().dh_format_alignment, sa.ctypes.data, sb.ctypes.data, o.ctypes.data, len(o), int(width))
 
 
 class DeviceTrace:

@@ -1,0 +1,359 @@
+// dh_editpath.cpp -- host side of the edit-path API (dh_la_edit_paths, dh_la_set_edit_paths, dh_edit_paths_*) and the
+// host-only formatters dh_format_cigar / dh_format_alignment.  The kernels are in dh_editpath.hip.
+//
+// A call validates every record against the two DBs, cuts the records into trace tiles and runs them chunk by chunk
+// (DH_EDIT_CHUNK tiles, a development knob): the tiles whose band fits a class go through k_edit_fast, the ones it does not
+// prove exact and the ones no class fits through k_edit_general, k_edit_compact puts the ops of the chunk in alignment
+// order, and the host appends them to the result.  Device scratch (arena slots 74..84) is bounded by the chunk.
+#include "dh_internal.h"
+
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "dh_editpath.h"
+
+extern "C" void dhk_edit_fast(hipStream_t st, int nw, const EpTile *tiles, int32_t n, const uint8_t *abases,
+                              const uint8_t *bfwd, const uint8_t *brc, int32_t rows, int32_t owords, uint64_t *dm,
+                              uint64_t *ow, EpResult *res);
+extern "C" void dhk_edit_general(hipStream_t st, const EpTile *tiles, int32_t n, const uint8_t *abases, const uint8_t *bfwd,
+                                 const uint8_t *brc, int32_t rows, uint32_t *dmat, const int64_t *ow_off, uint64_t *ow,
+                                 EpResult *res);
+extern "C" void dhk_edit_compact(hipStream_t st, const EpCopy *cp, int32_t n, const uint64_t *ow_fast, const uint64_t *ow_general,
+                                 uint8_t *out);
+
+struct dh_edit_paths {
+    std::vector<int64_t> op_off{0}, tile_off{0};
+    std::vector<uint8_t> ops;
+    std::vector<int32_t> score;
+    std::vector<uint16_t> tile_score;
+    int64_t general_tiles = 0;
+};
+
+extern "C" void dh_edit_paths_destroy(dh_edit_paths *p) { delete p; }
+extern "C" int64_t dh_edit_paths_count(const dh_edit_paths *p) { return p ? (int64_t)p->score.size() : 0; }
+extern "C" const int64_t *dh_edit_paths_op_off(const dh_edit_paths *p) { return p ? p->op_off.data() : nullptr; }
+extern "C" const uint8_t *dh_edit_paths_ops(const dh_edit_paths *p) { return p ? p->ops.data() : nullptr; }
+extern "C" const int32_t *dh_edit_paths_score(const dh_edit_paths *p) { return p ? p->score.data() : nullptr; }
+extern "C" const int64_t *dh_edit_paths_tile_off(const dh_edit_paths *p) { return p ? p->tile_off.data() : nullptr; }
+extern "C" const uint16_t *dh_edit_paths_tile_score(const dh_edit_paths *p) { return p ? p->tile_score.data() : nullptr; }
+extern "C" int64_t dh_edit_paths_general_tiles(const dh_edit_paths *p) { return p ? p->general_tiles : 0; }
+
+namespace {
+
+#define EP_GENERAL_BATCH 2048 /* tiles per launch of the full-matrix kernel: 64 KB of decisions each at tspace = 250 */
+
+template <typename T>
+int scr(dh_ctx *ctx, int id, size_t count, T **out)
+{
+    return dh_scratch(ctx, id, sizeof(T) * std::max<size_t>(count, 1), (void **)out);
+}
+
+// the tiles of record `idx` (dazzler.d:2405-2426: A from abpos to the next multiple of tspace, then in steps of tspace, the
+// last one ending at aepos; B the running sum of the trace's bbases), validated: nothing the kernels read lies outside
+// the sequences
+int cut_record(const dh_db *A, const dh_db *B, const dh_la &la, int64_t idx, const uint16_t *trace, int64_t trace_len,
+               int32_t ts, std::vector<EpTile> &tiles)
+{
+    char msg[256];
+#define EP_BAD(...)                                  \
+    do {                                             \
+        snprintf(msg, sizeof(msg), __VA_ARGS__);     \
+        return dh_fail(DH_EINVAL, msg);              \
+    } while (0)
+    if (la.aread < 0 || la.aread >= A->n || la.bread < 0 || la.bread >= B->n)
+        EP_BAD("dh_la_edit_paths: LA %lld: read numbers (%d, %d) outside the DBs", (long long)idx, la.aread, la.bread);
+    const int64_t alen = A->h_off[(size_t)la.aread + 1] - A->h_off[(size_t)la.aread];
+    const int64_t blen = B->h_off[(size_t)la.bread + 1] - B->h_off[(size_t)la.bread];
+    if (la.abpos < 0 || la.aepos < la.abpos || la.aepos > alen || la.bbpos < 0 || la.bepos < la.bbpos || la.bepos > blen)
+        EP_BAD("dh_la_edit_paths: LA %lld: coordinates [%d, %d) x [%d, %d) outside the sequences (%lld, %lld bases)",
+               (long long)idx, la.abpos, la.aepos, la.bbpos, la.bepos, (long long)alen, (long long)blen);
+    if (la.tlen < 0 || (la.tlen & 1)) EP_BAD("dh_la_edit_paths: LA %lld: tlen %d is odd or negative", (long long)idx, la.tlen);
+    if (la.toff < 0 || (trace_len >= 0 && la.toff + la.tlen > trace_len))
+        EP_BAD("dh_la_edit_paths: LA %lld: trace values [%lld, +%d) outside the trace", (long long)idx, (long long)la.toff, la.tlen);
+    const int32_t nt = la.tlen / 2;
+    const int32_t want = la.aepos > la.abpos ? (la.aepos + ts - 1) / ts - la.abpos / ts : nt;
+    if (nt != want || (la.aepos == la.abpos && nt > 1))
+        EP_BAD("dh_la_edit_paths: LA %lld: %d trace points for A [%d, %d) at tspace %d (%d expected)", (long long)idx, nt, la.abpos,
+               la.aepos, ts, want);
+    const uint16_t *tr = trace + la.toff;
+    int64_t bsum = 0;
+    for (int32_t t = 0; t < nt; t++) bsum += tr[2 * t + 1];
+    if (bsum != (int64_t)la.bepos - la.bbpos)
+        EP_BAD("dh_la_edit_paths: LA %lld: the trace's B bases sum to %lld, the record spans %d", (long long)idx, (long long)bsum,
+               la.bepos - la.bbpos);
+    const bool comp = (la.flags & DH_FLAG_COMP) != 0;
+    int32_t a = la.abpos, b = la.bbpos;
+    for (int32_t t = 0; t < nt; t++) {
+        const int32_t a1 = std::min<int32_t>((a / ts + 1) * ts, la.aepos), b1 = b + tr[2 * t + 1];
+        EpTile tl;
+        tl.aoff = A->h_off[(size_t)la.aread] + a;
+        tl.boff = B->h_off[(size_t)la.bread] + b;
+        tl.rl = a1 - a;
+        tl.ql = b1 - b;
+        tl.diffs = tr[2 * t];
+        tl.comp = comp ? 1 : 0;
+        if (tl.ql > EP_QL_FACTOR * ts)
+            EP_BAD("dh_la_edit_paths: LA %lld tile %d: %d B bases against %d A bases exceed the cap of %d x tspace", (long long)idx, t,
+                   tl.ql, tl.rl, EP_QL_FACTOR);
+        tiles.push_back(tl);
+        a = a1;
+        b = b1;
+    }
+    return DH_OK;
+#undef EP_BAD
+}
+
+struct ChunkRun {
+    dh_ctx *ctx;
+    dh_db *A, *B;
+    int32_t ts;
+};
+
+// tiles [t0, t1) of `tiles` (alignment order): nops / score per tile into res[], the ops appended to out->ops
+int run_chunk(const ChunkRun &r, const std::vector<EpTile> &tiles, size_t t0, size_t t1, std::vector<EpResult> &res,
+              dh_edit_paths *out)
+{
+    dh_ctx *ctx = r.ctx;
+    hipStream_t st = ctx->stream;
+    const size_t n = t1 - t0;
+    const uint8_t *ab = r.A->d_bases, *bf = r.B->d_bases, *brc = r.B->d_rc;
+    // ---- fast path: class 1, then class 2, each its own launch
+    std::vector<int32_t> idx[3];
+    for (size_t t = 0; t < n; t++) idx[ep::tile_class(tiles[t0 + t].rl, tiles[t0 + t].ql, tiles[t0 + t].diffs)].push_back((int32_t)t);
+    std::vector<EpCopy> cp(n);
+    std::vector<EpTile> stage;
+    std::vector<EpResult> fres;
+    const size_t nfast = idx[1].size() + idx[2].size();
+    size_t wbase[3] = {0, 0, 0};
+    uint64_t *d_ow = nullptr;
+    if (nfast) {
+        int32_t rows[3] = {0, 0, 0}, owords[3] = {0, 0, 0};
+        stage.reserve(nfast);
+        for (int c = 1; c <= 2; c++)
+            for (int32_t t : idx[c]) {
+                const EpTile &tl = tiles[t0 + (size_t)t];
+                rows[c] = std::max(rows[c], tl.rl);
+                owords[c] = std::max(owords[c], (tl.rl + tl.ql + 7) >> 3);
+                stage.push_back(tl);
+            }
+        const size_t n1 = idx[1].size(), n2 = idx[2].size();
+        const size_t dm1 = n1 * (size_t)rows[1] * 3, dm2 = n2 * (size_t)rows[2] * 6;
+        wbase[1] = 0;
+        wbase[2] = n1 * (size_t)owords[1];
+        EpTile *d_tiles;
+        uint64_t *d_dm;
+        EpResult *d_res;
+        if (int rc = scr(ctx, 74, nfast, &d_tiles)) return rc;
+        if (int rc = scr(ctx, 75, dm1 + dm2, &d_dm)) return rc;
+        if (int rc = scr(ctx, 76, wbase[2] + n2 * (size_t)owords[2], &d_ow)) return rc;
+        if (int rc = scr(ctx, 77, nfast, &d_res)) return rc;
+        HIPCHK(hipMemcpyAsync(d_tiles, stage.data(), sizeof(EpTile) * nfast, hipMemcpyHostToDevice, st));
+        dhk_edit_fast(st, 1, d_tiles, (int32_t)n1, ab, bf, brc, rows[1], owords[1], d_dm, d_ow, d_res);
+        dhk_edit_fast(st, 2, d_tiles + n1, (int32_t)n2, ab, bf, brc, rows[2], owords[2], d_dm + dm1, d_ow + wbase[2], d_res + n1);
+        HIPCHK(hipGetLastError());
+        fres.resize(nfast);
+        HIPCHK(hipMemcpyAsync(fres.data(), d_res, sizeof(EpResult) * nfast, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        size_t k = 0;
+        for (int c = 1; c <= 2; c++) {
+            const size_t nc = idx[c].size();
+            for (size_t p = 0; p < nc; p++, k++) {
+                const int32_t t = idx[c][p];
+                if (fres[k].nops & EP_REJECTED) {
+                    idx[0].push_back(t);
+                    continue;
+                }
+                res[t0 + (size_t)t] = fres[k];
+                cp[(size_t)t] = EpCopy{(int64_t)(wbase[c] + p), (int64_t)nc, 0, (int32_t)fres[k].nops, 0};
+            }
+        }
+    }
+    // ---- general path: what no class fits and what the fast path could not prove exact
+    uint64_t *d_gow = nullptr;
+    if (!idx[0].empty()) {
+        const size_t ng = idx[0].size();
+        out->general_tiles += (int64_t)ng;
+        std::vector<int64_t> goff(ng + 1, 0);
+        stage.clear();
+        int32_t rows = 1;
+        for (size_t p = 0; p < ng; p++) {
+            const EpTile &tl = tiles[t0 + (size_t)idx[0][p]];
+            stage.push_back(tl);
+            rows = std::max(rows, tl.rl);
+            goff[p + 1] = goff[p] + ((tl.rl + tl.ql + 7) >> 3);
+        }
+        const size_t gb = std::min<size_t>(ng, EP_GENERAL_BATCH);
+        EpTile *d_tiles;
+        int64_t *d_goff;
+        uint32_t *d_dm;
+        EpResult *d_res;
+        if (int rc = scr(ctx, 78, ng, &d_tiles)) return rc;
+        if (int rc = scr(ctx, 79, gb * (size_t)rows * 64, &d_dm)) return rc;
+        if (int rc = scr(ctx, 80, (size_t)goff[ng], &d_gow)) return rc;
+        if (int rc = scr(ctx, 81, ng + 1, &d_goff)) return rc;
+        if (int rc = scr(ctx, 83, ng, &d_res)) return rc;
+        HIPCHK(hipMemcpyAsync(d_tiles, stage.data(), sizeof(EpTile) * ng, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_goff, goff.data(), sizeof(int64_t) * (ng + 1), hipMemcpyHostToDevice, st));
+        for (size_t g0 = 0; g0 < ng; g0 += gb)  // (one stream: a batch starts when the one before it is done with d_dm)
+            dhk_edit_general(st, d_tiles + g0, (int32_t)std::min(gb, ng - g0), ab, bf, brc, rows, d_dm, d_goff + g0, d_gow, d_res + g0);
+        HIPCHK(hipGetLastError());
+        fres.resize(ng);
+        HIPCHK(hipMemcpyAsync(fres.data(), d_res, sizeof(EpResult) * ng, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t p = 0; p < ng; p++) {
+            const int32_t t = idx[0][p];
+            if (fres[p].nops & EP_REJECTED) return dh_fail(DH_EINVAL, "dh_la_edit_paths: a tile exceeds the full-matrix kernel's caps");
+            res[t0 + (size_t)t] = fres[p];
+            cp[(size_t)t] = EpCopy{goff[p], 1, 0, (int32_t)fres[p].nops, 1};
+        }
+    }
+    // ---- the ops of the chunk in alignment order
+    int64_t total = 0;
+    for (size_t t = 0; t < n; t++) {
+        cp[t].out = total;
+        total += cp[t].nops;
+    }
+    if (total == 0) return DH_OK;
+    EpCopy *d_cp;
+    uint8_t *d_out;
+    if (int rc = scr(ctx, 82, n, &d_cp)) return rc;
+    if (int rc = scr(ctx, 84, (size_t)total, &d_out)) return rc;
+    HIPCHK(hipMemcpyAsync(d_cp, cp.data(), sizeof(EpCopy) * n, hipMemcpyHostToDevice, st));
+    dhk_edit_compact(st, d_cp, (int32_t)n, d_ow, d_gow, d_out);
+    HIPCHK(hipGetLastError());
+    const size_t at = out->ops.size();
+    out->ops.resize(at + (size_t)total);
+    HIPCHK(hipMemcpyAsync(out->ops.data() + at, d_out, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return DH_OK;
+}
+
+int edit_paths_impl(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la *las, int64_t n, const uint16_t *trace, int64_t trace_len,
+                    int32_t ts, int64_t first, int64_t count, dh_edit_paths **out)
+{
+    if (!ctx || !A || !B || !out || n < 0 || first < 0 || count < 0 || first + count > n || (count > 0 && (!las || !trace)))
+        return dh_fail(DH_EINVAL, "dh_la_edit_paths: bad argument");
+    if (ts < 1 || ts > EP_TSPACE_MAX) return dh_fail(DH_EINVAL, "dh_la_edit_paths: tspace must be in [1, 250]");
+    *out = nullptr;
+    // ---- validation and tiling on the host, before anything is launched
+    std::unique_ptr<dh_edit_paths> p(new dh_edit_paths);
+    std::vector<EpTile> tiles;
+    p->score.assign((size_t)count, 0);
+    p->op_off.assign((size_t)count + 1, 0);
+    p->tile_off.assign((size_t)count + 1, 0);
+    for (int64_t i = 0; i < count; i++) {
+        if (int rc = cut_record(A, B, las[first + i], first + i, trace, trace_len, ts, tiles)) return rc;
+        p->tile_off[(size_t)i + 1] = (int64_t)tiles.size();
+    }
+    p->tile_score.assign(tiles.size(), 0);
+    if (!tiles.empty()) {
+        HIPCHK(hipSetDevice(ctx->device));
+        if (int rc = dh_ensure_rc(B)) return rc;
+        size_t chunk = 131072;
+        if (const char *e = getenv("DH_EDIT_CHUNK")) chunk = (size_t)std::max(1, atoi(e));  // development
+        std::vector<EpResult> res(tiles.size());
+        const ChunkRun r{ctx, A, B, ts};
+        for (size_t t0 = 0; t0 < tiles.size(); t0 += chunk)
+            if (int rc = run_chunk(r, tiles, t0, std::min(tiles.size(), t0 + chunk), res, p.get())) return rc;
+        for (int64_t i = 0; i < count; i++) {
+            int64_t nops = 0, score = 0;
+            for (int64_t t = p->tile_off[(size_t)i]; t < p->tile_off[(size_t)i + 1]; t++) {
+                nops += res[(size_t)t].nops;
+                score += res[(size_t)t].score;
+                p->tile_score[(size_t)t] = (uint16_t)res[(size_t)t].score;
+            }
+            p->op_off[(size_t)i + 1] = p->op_off[(size_t)i] + nops;
+            p->score[(size_t)i] = (int32_t)score;
+        }
+    }
+    *out = p.release();
+    return DH_OK;
+}
+
+}  // namespace
+
+extern "C" int dh_la_edit_paths(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la *las, int64_t n, const uint16_t *trace,
+                                int32_t tspace, int64_t first, int64_t count, dh_edit_paths **out)
+{
+    return edit_paths_impl(ctx, A, B, las, n, trace, -1, tspace, first, count, out);
+}
+
+extern "C" int dh_la_set_edit_paths(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la_set *set, int64_t first, int64_t count,
+                                    dh_edit_paths **out)
+{
+    if (!set) return dh_fail(DH_EINVAL, "dh_la_set_edit_paths: set is NULL");
+    if (set->la.empty() && set->d_la_n > 0)
+        return dh_fail(DH_EINVAL, "dh_la_set_edit_paths: the records of this set were left on the device");
+    if (int rc = dh_la_set_ensure_host_trace(const_cast<dh_la_set *>(set))) return rc;
+    return edit_paths_impl(ctx, A, B, set->la.data(), (int64_t)set->la.size(), set->trace.data(), (int64_t)set->trace.size(),
+                           set->tspace, first, count, out);
+}
+
+// ------------------------------------------------------------------------------------ formatters (host only)
+
+extern "C" int64_t dh_format_cigar(const uint8_t *ops, int64_t nops, int32_t extended, char *out, int64_t cap)
+{
+    if (nops < 0 || (nops > 0 && !ops)) return dh_fail(DH_EINVAL, "dh_format_cigar: bad argument");
+    std::string s;
+    for (int64_t i = 0; i < nops;) {
+        if (ops[i] > EP_OP_MISMATCH) return dh_fail(DH_EINVAL, "dh_format_cigar: op code above 3");
+        auto sym = [&](uint8_t op) {
+            return op == EP_OP_DEL ? 'D' : (op == EP_OP_INS ? 'I' : (!extended ? 'M' : (op == EP_OP_MATCH ? '=' : 'X')));
+        };
+        const char c = sym(ops[i]);
+        int64_t j = i + 1;
+        while (j < nops && ops[j] <= EP_OP_MISMATCH && sym(ops[j]) == c) j++;
+        s += std::to_string(j - i);
+        s += c;
+        i = j;
+    }
+    if (out && cap > (int64_t)s.size()) memcpy(out, s.c_str(), s.size() + 1);
+    return (int64_t)s.size();
+}
+
+extern "C" int64_t dh_format_alignment(const uint8_t *a, const uint8_t *b, const uint8_t *ops, int64_t nops, int32_t width,
+                                       char *out, int64_t cap)
+{
+    if (nops < 0 || width < 0 || (nops > 0 && (!ops || !a || !b))) return dh_fail(DH_EINVAL, "dh_format_alignment: bad argument");
+    // SequenceAlignment.toString (util/string.d:365-426): reference line, compare line, query line; blocks of `width`
+    // columns separated by an empty line, no newline at the end.  Base codes 0..4 print as acgtn, other bytes as they are.
+    auto chr = [](uint8_t x) { return x < 5 ? "acgtn"[x] : (char)x; };
+    std::string l[3];
+    for (int k = 0; k < 3; k++) l[k].reserve((size_t)nops);
+    int64_t i = 0, j = 0;
+    for (int64_t k = 0; k < nops; k++) switch (ops[k]) {
+            case EP_OP_MATCH:
+            case EP_OP_MISMATCH:
+                l[0] += chr(a[i++]);
+                l[1] += ops[k] == EP_OP_MATCH ? '|' : '*';
+                l[2] += chr(b[j++]);
+                break;
+            case EP_OP_DEL:
+                l[0] += chr(a[i++]);
+                l[1] += ' ';
+                l[2] += '-';
+                break;
+            case EP_OP_INS:
+                l[0] += '-';
+                l[1] += ' ';
+                l[2] += chr(b[j++]);
+                break;
+            default:
+                return dh_fail(DH_EINVAL, "dh_format_alignment: op code above 3");
+        }
+    std::string s;
+    if (width == 0) {
+        s = l[0] + "\n" + l[1] + "\n" + l[2];
+    } else {
+        for (int64_t c0 = 0; c0 < nops; c0 += width) {
+            if (c0) s += "\n\n";
+            for (int k = 0; k < 3; k++) {
+                if (k) s += "\n";
+                s += l[k].substr((size_t)c0, (size_t)width);
+            }
+        }
+    }
+    if (out && cap > (int64_t)s.size()) memcpy(out, s.c_str(), s.size() + 1);
+    return (int64_t)s.size();
+}

@@ -670,6 +670,42 @@ int dh_tile_qv(dh_ctx *ctx, dh_db *db, const dh_la *las, int64_t n, const uint16
 int dh_consensus(dh_ctx *ctx, dh_db *db, const dh_la *las, int64_t n, const uint16_t *trace, int32_t tspace,
                  int32_t ref_read, int32_t rounds, uint8_t *out, int64_t cap, int64_t *out_len);
 
+/* ---- base-level alignments from trace points: getExactAlignment's per-trace-point part (dazzler.d:2405-2426) for the
+ *      records [first, first + count) of las.  Every trace tile of a record (A from abpos to the next multiple of
+ *      tspace, then in steps of tspace, ending at aepos; B the running sum of the trace's B bases; COMP records in the
+ *      reverse-complement frame of the B read) is aligned by findAlignment(a, b, indelPenalty = 1, No.freeShift) with
+ *      its traceback rule (util/string.d:478-520, 775-831), the tile results are concatenated.  One byte per op:
+ *      0 match, 1 deletion (A base without B base), 2 insertion (B base without A base), 3 mismatch.
+ *        op_off[i] .. op_off[i + 1]      ops of record first + i, in alignment order
+ *        score[i]                        sum of its tiles' scores = its number of non-zero ops
+ *        tile_off[i] .. tile_off[i + 1]  its tiles in tile_score (the exact edit distance of each tile)
+ *        general_tiles                   tiles the banded kernel could not prove exact from the trace's diffs (band =
+ *                                        diffs + 1 at most 63) and the full-matrix kernel aligned instead
+ *      Limits: tspace <= 250, a tile's B side <= 4 x tspace.  A malformed record (odd tlen, a tile count that disagrees
+ *      with abpos / aepos, B bases that do not sum to bepos - bbpos, coordinates outside the sequences, a tile over
+ *      the limits) is DH_EINVAL, found on the host before anything is launched; dh_last_error names the record.
+ *      dh_format_cigar / dh_format_alignment are host only and need no device: runs of =, X, I, D (extended != 0) or
+ *      M, I, D; SequenceAlignment.toString(width)'s three lines per block ('|' match, '*' mismatch, ' ' and '-' for
+ *      gaps; a / b: base codes 0..4 print as acgtn, other bytes as they are).  Both return the length of the text
+ *      (without the terminating 0) and write it only when out is not NULL and cap is larger than that; a negative
+ *      value is an error code. */
+typedef struct dh_edit_paths dh_edit_paths;
+int dh_la_edit_paths(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la *las, int64_t n, const uint16_t *trace,
+                     int32_t tspace, int64_t first, int64_t count, dh_edit_paths **out);
+int dh_la_set_edit_paths(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la_set *set, int64_t first, int64_t count,
+                         dh_edit_paths **out);
+void dh_edit_paths_destroy(dh_edit_paths *p);
+int64_t dh_edit_paths_count(const dh_edit_paths *p);
+const int64_t *dh_edit_paths_op_off(const dh_edit_paths *p);    /* count + 1 */
+const uint8_t *dh_edit_paths_ops(const dh_edit_paths *p);
+const int32_t *dh_edit_paths_score(const dh_edit_paths *p);     /* per LA: sum of its tiles' NW scores */
+const int64_t *dh_edit_paths_tile_off(const dh_edit_paths *p);  /* count + 1 */
+const uint16_t *dh_edit_paths_tile_score(const dh_edit_paths *p);
+int64_t dh_edit_paths_general_tiles(const dh_edit_paths *p);
+int64_t dh_format_cigar(const uint8_t *ops, int64_t nops, int32_t extended, char *out, int64_t cap);
+int64_t dh_format_alignment(const uint8_t *a, const uint8_t *b, const uint8_t *ops, int64_t nops, int32_t width,
+                            char *out, int64_t cap);
+
 /* ---- gap-closed assembly writer (host only): the linear-scaffold subset of `dentist output`
  *      (source/dentist/commands/output.d:743-925): header "<id>\tscaffold-<first contig id>", contig
  *      slices lower case, insertions upper case (highlight != 0), unclosed gaps as 'n' runs, lines

@@ -21,6 +21,9 @@
 //                                    DB's track (snakemake/Snakefile:1111-1123; track layout dazzler.d:4943-5170)
 //   TANmask [-v] [-l<int(500)>] [-n<track(tan)>] <db> <TAN las>...   self alignments of a read -> mask intervals
 //                                    (snakemake/Snakefile:1095-1108); the block's track when the .las names a block
+//   LApaf [-a] [-w<int(100)>] <A:db|dam> [<B:db|dam>] <align:las> [first-last]   base-level alignments of the records of a
+//                                    .las as PAF with an extended cigar (dh_la_edit_paths: getExactAlignment's per-trace-point
+//                                    part, dazzler.d:2405-2426); -a adds the alignment text (SequenceAlignment.toString)
 // DENTIST only sees exit codes, files and stdout of these tools; flags it never emits are rejected.
 #include <algorithm>
 #include <cmath>
@@ -714,6 +717,124 @@ static int tool_merge_insertions(const std::vector<std::string> &args)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- LApaf
+// One PAF line per record: the query is the B read (strand '-' and coordinates turned back to the forward strand for
+// complement records), the target the A sequence; names are the first word of the FASTA header (DAM) or the prolog (DB)
+// followed by /<1-based read number>.  Tags: NM:i the exact edit distance summed over the trace tiles, tp:i the sum of the
+// trace's diffs (what the aligner's band found), cg:Z the extended cigar (= X I D).
+static std::string paf_name(const dh_dazz *d, int32_t i)
+{
+    const char *h = dh_dazz_header(d, i);
+    std::string s = h ? h : "";
+    if (!s.empty() && s[0] == '>') s.erase(0, 1);
+    const size_t e = s.find_first_of(" \t\n");
+    if (e != std::string::npos) s.resize(e);
+    if (s.empty()) s = "read";
+    return s + "/" + std::to_string(dh_dazz_first_id(d) + i + 1);
+}
+
+static int tool_lapaf(const std::vector<std::string> &args)
+{
+    bool show = false;
+    int width = 100;
+    std::vector<std::string> pos;
+    for (const std::string &a : args) {
+        if (a == "-a")
+            show = true;
+        else if (a.compare(0, 2, "-w") == 0)
+            width = atoi(a.c_str() + 2);
+        else if (a[0] == '-')
+            die("unknown option " + a);
+        else
+            pos.push_back(a);
+    }
+    long long r0 = 1, r1 = -1;
+    if (pos.size() >= 3 && pos.back().find_first_not_of("0123456789-") == std::string::npos) {
+        if (sscanf(pos.back().c_str(), "%lld-%lld", &r0, &r1) != 2) {
+            if (sscanf(pos.back().c_str(), "%lld", &r0) != 1) die("bad record range " + pos.back());
+            r1 = r0;
+        }
+        pos.pop_back();
+    }
+    if (pos.size() < 2 || pos.size() > 3 || width < 1) die("usage: LApaf [-a] [-w<int(100)>] <A:db|dam> [<B:db|dam>] <align:las> [first-last]");
+    const bool two = pos.size() == 3 && pos[1] != pos[0];
+    Dev va = open_dev(pos[0]);
+    Dev vb;
+    if (two) {
+        vb.dz = open_dazz(pos[1]);
+        CHK(dh_db_create(va.ctx, dh_dazz_bases(vb.dz), dh_dazz_offsets(vb.dz), dh_dazz_nreads(vb.dz), nullptr, &vb.db));
+    }
+    const dh_dazz *da = va.dz, *dbz = two ? vb.dz : va.dz;
+    dh_db *A = va.db, *B = two ? vb.db : va.db;
+    dh_la_set *set = nullptr;
+    CHK(dh_las_read(pos.back().c_str(), &set));
+    const int64_t n = dh_la_set_count(set);
+    std::vector<dh_la> las(dh_la_set_records(set), dh_la_set_records(set) + n);
+    for (dh_la &l : las) {
+        l.aread -= dh_dazz_first_id(da);
+        l.bread -= dh_dazz_first_id(dbz);
+    }
+    if (r1 < 0) r1 = n;
+    if (r0 < 1 || r1 > n || r0 > r1 + 1) die("record range outside the file (" + std::to_string(n) + " records)");
+    const uint16_t *trace = dh_la_set_trace(set);
+    const int32_t ts = dh_la_set_tspace(set);
+    dh_edit_paths *ep = nullptr;
+    CHK(dh_la_edit_paths(va.ctx, A, B, las.data(), n, trace, ts, r0 - 1, r1 - r0 + 1, &ep));
+    const int64_t *op_off = dh_edit_paths_op_off(ep);
+    const uint8_t *ops = dh_edit_paths_ops(ep);
+    const int32_t *score = dh_edit_paths_score(ep);
+    const int64_t *aoff = dh_dazz_offsets(da), *boff = dh_dazz_offsets(dbz);
+    std::vector<char> text;
+    std::vector<uint8_t> brc;
+    for (int64_t i = 0; i < dh_edit_paths_count(ep); i++) {
+        const dh_la &l = las[(size_t)(r0 - 1 + i)];
+        const uint8_t *o = ops + op_off[i];
+        const int64_t no = op_off[i + 1] - op_off[i];
+        const int64_t alen = aoff[l.aread + 1] - aoff[l.aread], blen = boff[l.bread + 1] - boff[l.bread];
+        const bool comp = (l.flags & DH_FLAG_COMP) != 0;
+        int64_t nmatch = 0, tdiffs = 0;
+        for (int64_t k = 0; k < no; k++) nmatch += o[k] == 0;
+        for (int32_t t = 0; t < l.tlen; t += 2) tdiffs += trace[l.toff + t];
+        const int64_t clen = dh_format_cigar(o, no, 1, nullptr, 0);
+        if (clen < 0) die(dh_last_error());
+        text.resize((size_t)clen + 1);
+        dh_format_cigar(o, no, 1, text.data(), clen + 1);
+        printf("%s\t%lld\t%lld\t%lld\t%c\t%s\t%lld\t%d\t%d\t%lld\t%lld\t255\tNM:i:%d\ttp:i:%lld\tcg:Z:%s\n", paf_name(dbz, l.bread).c_str(),
+               (long long)blen, (long long)(comp ? blen - l.bepos : l.bbpos), (long long)(comp ? blen - l.bbpos : l.bepos),
+               comp ? '-' : '+', paf_name(da, l.aread).c_str(), (long long)alen, l.abpos, l.aepos, (long long)nmatch, (long long)no,
+               score[i], (long long)tdiffs, text.data());
+        if (!show) continue;
+        const uint8_t *a = dh_dazz_bases(da) + aoff[l.aread] + l.abpos, *b = dh_dazz_bases(dbz) + boff[l.bread] + l.bbpos;
+        if (comp) {  // the B side of the record in the reverse-complement frame
+            brc.resize((size_t)(l.bepos - l.bbpos));
+            const uint8_t *fwd = dh_dazz_bases(dbz) + boff[l.bread];
+            for (int32_t x = l.bbpos; x < l.bepos; x++) {
+                const uint8_t c = fwd[blen - 1 - x];
+                brc[(size_t)(x - l.bbpos)] = c < 4 ? (uint8_t)(3 - c) : c;
+            }
+            b = brc.data();
+        }
+        const int64_t tl = dh_format_alignment(a, b, o, no, width, nullptr, 0);
+        if (tl < 0) die(dh_last_error());
+        text.resize((size_t)tl + 1);
+        dh_format_alignment(a, b, o, no, width, text.data(), tl + 1);
+        putchar('#');
+        for (int64_t k = 0; k < tl; k++) {
+            putchar(text[(size_t)k]);
+            if (text[(size_t)k] == '\n') putchar('#');
+        }
+        putchar('\n');
+    }
+    dh_edit_paths_destroy(ep);
+    dh_la_set_destroy(set);
+    if (two) {
+        dh_db_destroy(vb.db);
+        dh_dazz_close(vb.dz);
+    }
+    close_dev(va);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     g_tool = argv[0];
@@ -741,6 +862,7 @@ int main(int argc, char **argv)
     if (g_tool == "LAsplit") return tool_lasplit(args);
     if (g_tool == "Catrack") return tool_catrack(args);
     if (g_tool == "TANmask") return tool_tanmask(args);
+    if (g_tool == "LApaf") return tool_lapaf(args);
     die("unknown tool (expected fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv "
         "computeintrinsicqv daccord merge-insertions)");
     return 1;
