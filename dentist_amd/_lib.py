@@ -97,7 +97,7 @@ SYMBOLS = [
     "dh_crop_pileups_masked", "dh_process_pileups_masked", "dh_process_pileups_set", "dh_la_set_trace_on_device", "dh_scaffold_graph_probe",
     "dh_la_edit_paths", "dh_la_set_edit_paths", "dh_edit_paths_destroy", "dh_edit_paths_count", "dh_edit_paths_op_off",
     "dh_edit_paths_ops", "dh_edit_paths_score", "dh_edit_paths_tile_off", "dh_edit_paths_tile_score",
-    "dh_edit_paths_general_tiles", "dh_format_cigar", "dh_format_alignment",
+    "dh_edit_paths_general_tiles", "dh_format_cigar", "dh_format_alignment", "dh_la_transpose", "dh_la_set_transpose",
 ]
 
 _LIB = None
@@ -209,6 +209,8 @@ def lib():
     L.dh_dazz_header.restype = ctypes.c_char_p
     L.dh_la_edit_paths.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, i64, ctypes.POINTER(vp)]
     L.dh_la_set_edit_paths.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.POINTER(vp)]
+    L.dh_la_transpose.argtypes = [vp, vp, vp, vp, i64, vp, i32, i32, ctypes.POINTER(vp), vp]
+    L.dh_la_set_transpose.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     L.dh_edit_paths_destroy.argtypes = [vp]
     L.dh_edit_paths_destroy.restype = None
     for fn in (L.dh_edit_paths_count, L.dh_edit_paths_general_tiles):
@@ -388,6 +390,24 @@ class Context:
             _check(L.dh_la_edit_paths(self._h, A._h, B._h, arr.ctypes.data, len(arr), tr.ctypes.data, int(tspace), int(first),
                                       int(count), ctypes.byref(h)))
         return EditPaths(h)
+
+    def transpose(self, A, B, las, trace=None, tspace=None, select_best=False):
+        """dh_la_transpose: the same alignments with the roles of the sequences exchanged (aread = B read, trace points on
+        the B read's grid), from their edit paths.  Returns (las', trace', src_index), LAsort order; src_index[i] is the
+        source record of las'[i].  `las` may be a raw handle of align_db_block(..., raw=True) (dh_la_set_transpose)."""
+        h = ctypes.c_void_p()
+        L = lib()
+        if isinstance(las, ctypes.c_void_p):
+            src = np.zeros(L.dh_la_set_count(las), dtype=np.int64)
+            _check(L.dh_la_set_transpose(self._h, A._h, B._h, las, int(select_best), ctypes.byref(h), src.ctypes.data))
+        else:
+            arr = np.ascontiguousarray(las, dtype=LA_DTYPE)
+            tr = np.ascontiguousarray(trace, dtype=np.uint16)
+            src = np.zeros(len(arr), dtype=np.int64)
+            _check(L.dh_la_transpose(self._h, A._h, B._h, arr.ctypes.data, len(arr), tr.ctypes.data, int(tspace),
+                                     int(select_best), ctypes.byref(h), src.ctypes.data))
+        out, otr, _ = _take_la_set(h)
+        return out, otr, src
 
     def align_db_block(self, A, B, first, count, opts, select_best=False, raw=False):
         """`damapper ref reads.<block>`: reads [first, first + count) of B against A.  raw=True

@@ -1043,6 +1043,28 @@ static void select_best_range(dh_la *la, size_t nla, int32_t near_ppm)
     });
 }
 
+int32_t dh_ctx_near_best_ppm(const dh_ctx *ctx) { return ctx->near_best_ppm >= 0 ? ctx->near_best_ppm : g_near_best_ppm.load(); }
+
+// chain flags of a set of transposed records (aread = read, bread = contig), grouped by aread: the same rule with the
+// roles of the sequences exchanged (chains of a read on one contig, ordered along the read); then LAsort order
+void dh_finish_transposed_set(dh_la_set *set, bool want_best, int32_t near_ppm)
+{
+    auto swap_roles = [&]() {
+        for (dh_la &l : set->la) {
+            std::swap(l.aread, l.bread);
+            std::swap(l.abpos, l.bbpos);
+            std::swap(l.aepos, l.bepos);
+        }
+    };
+    if (want_best) {
+        swap_roles();
+        select_best_range(set->la.data(), set->la.size(), near_ppm);
+        swap_roles();
+    }
+    std::sort(set->la.begin(), set->la.end(), la_less);
+}
+bool dh_la_less(const dh_la &p, const dh_la &q) { return la_less(p, q); }
+
 // LAsort order of a B-major (bread, strand, ...) list in O(n): stable counting sort by aread
 // keeps (bread, comp) ascending inside every aread; the rare runs with equal (aread, bread, comp)
 // are finished with an insertion sort.
@@ -1355,7 +1377,7 @@ struct AlignRun {
     AlignRun(dh_ctx *ctx_, dh_db *A_, dh_db *B_, const dh_align_opts &o_, int32_t first_, int32_t count_, int32_t want_best_,
              int32_t want_sorted_, const ChunkHook *hook_)
         : ctx(ctx_), A(A_), B(B_), o(o_), first(first_), count(count_), want_best(want_best_), want_sorted(want_sorted_),
-          hook(hook_), st(ctx_->stream), near_ppm(ctx_->near_best_ppm >= 0 ? ctx_->near_best_ppm : g_near_best_ppm.load()),
+          hook(hook_), st(ctx_->stream), near_ppm(dh_ctx_near_best_ppm(ctx_)),
           tasks{ctx_->cstream, {}}, tiled(o_.algo == 1), nitems_total(2ll * count_), item_first(2ll * first_),
           item_end(2ll * first_ + 2ll * count_)
     {
@@ -2448,23 +2470,7 @@ static int finish_align(AlignRun &r, double wall0)
     const double tail_hooks = r.tasks.ms_hooks, tail_copies = r.tasks.ms_copies;
     if (r.want_best && !r.hook) select_best_range(res->la.data(), res->la.size(), near_ppm);
     if (r.want_sorted & 1) lasort(res, A->n);
-    if (res2) {
-        // chain flags of the transposed set: the same rule with the roles of the sequences exchanged (chains of a read
-        // on one contig, ordered along the read); then LAsort order
-        auto swap_roles = [&]() {
-            for (dh_la &l : res2->la) {
-                std::swap(l.aread, l.bread);
-                std::swap(l.abpos, l.bbpos);
-                std::swap(l.aepos, l.bepos);
-            }
-        };
-        if (r.want_best) {
-            swap_roles();  // grouped by read already (items are (read, strand) in order)
-            select_best_range(res2->la.data(), res2->la.size(), near_ppm);
-            swap_roles();
-        }
-        std::sort(res2->la.begin(), res2->la.end(), la_less);
-    }
+    if (res2) dh_finish_transposed_set(res2, r.want_best != 0, near_ppm);  // (grouped by read already: items are (read, strand) in order)
     r.w_post = now_ms() - w_a;
     stats.las = res->d_la_n > 0 ? res->d_la_n : (int64_t)res->la.size();
     float t;

@@ -5,6 +5,10 @@
 // (DH_EDIT_CHUNK tiles, a development knob): the tiles whose band fits a class go through k_edit_fast, the ones it does not
 // prove exact and the ones no class fits through k_edit_general, k_edit_compact puts the ops of the chunk in alignment
 // order, and the host appends them to the result.  Device scratch (arena slots 74..84) is bounded by the chunk.
+//
+// dh_la_transpose / dh_la_set_transpose run the same chunks cut between records, leave the ops of a chunk on the device
+// and let k_trace_transpose put the trace points of every record's transposed path on the grid of the B read (slots
+// 85..88); the host adds the coordinates, the chain flags and LAsort order.
 #include "dh_internal.h"
 
 #include <stdio.h>
@@ -21,6 +25,8 @@ extern "C" void dhk_edit_general(hipStream_t st, const EpTile *tiles, int32_t n,
                                  EpResult *res);
 extern "C" void dhk_edit_compact(hipStream_t st, const EpCopy *cp, int32_t n, const uint64_t *ow_fast, const uint64_t *ow_general,
                                  uint8_t *out);
+extern "C" void dhk_trace_transpose(hipStream_t st, const EpTrRec *recs, int32_t n, const uint8_t *ops, int32_t ts, uint2 *bound,
+                                    uint32_t *pairs, int32_t *status);
 
 struct dh_edit_paths {
     std::vector<int64_t> op_off{0}, tile_off{0};
@@ -104,15 +110,23 @@ int cut_record(const dh_db *A, const dh_db *B, const dh_la &la, int64_t idx, con
 #undef EP_BAD
 }
 
+size_t edit_chunk()  // tiles per launch
+{
+    if (const char *e = getenv("DH_EDIT_CHUNK")) return (size_t)std::max(1, atoi(e));  // development
+    return 131072;
+}
+
 struct ChunkRun {
     dh_ctx *ctx;
     dh_db *A, *B;
     int32_t ts;
 };
 
-// tiles [t0, t1) of `tiles` (alignment order): nops / score per tile into res[], the ops appended to out->ops
+// tiles [t0, t1) of `tiles` (alignment order): nops / score per tile into res[], the ops appended to out->ops -- or, with
+// keep_ops, left on the device (slot 84, tile after tile: a tile's first op is the sum of the nops before it) for a kernel
+// queued behind this call; *keep_ops is NULL when the chunk has no op
 int run_chunk(const ChunkRun &r, const std::vector<EpTile> &tiles, size_t t0, size_t t1, std::vector<EpResult> &res,
-              dh_edit_paths *out)
+              dh_edit_paths *out, const uint8_t **keep_ops = nullptr)
 {
     dh_ctx *ctx = r.ctx;
     hipStream_t st = ctx->stream;
@@ -214,6 +228,7 @@ int run_chunk(const ChunkRun &r, const std::vector<EpTile> &tiles, size_t t0, si
         cp[t].out = total;
         total += cp[t].nops;
     }
+    if (keep_ops) *keep_ops = nullptr;
     if (total == 0) return DH_OK;
     EpCopy *d_cp;
     uint8_t *d_out;
@@ -222,6 +237,10 @@ int run_chunk(const ChunkRun &r, const std::vector<EpTile> &tiles, size_t t0, si
     HIPCHK(hipMemcpyAsync(d_cp, cp.data(), sizeof(EpCopy) * n, hipMemcpyHostToDevice, st));
     dhk_edit_compact(st, d_cp, (int32_t)n, d_ow, d_gow, d_out);
     HIPCHK(hipGetLastError());
+    if (keep_ops) {
+        *keep_ops = d_out;
+        return DH_OK;
+    }
     const size_t at = out->ops.size();
     out->ops.resize(at + (size_t)total);
     HIPCHK(hipMemcpyAsync(out->ops.data() + at, d_out, (size_t)total, hipMemcpyDeviceToHost, st));
@@ -250,8 +269,7 @@ int edit_paths_impl(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la *las, int64_t n
     if (!tiles.empty()) {
         HIPCHK(hipSetDevice(ctx->device));
         if (int rc = dh_ensure_rc(B)) return rc;
-        size_t chunk = 131072;
-        if (const char *e = getenv("DH_EDIT_CHUNK")) chunk = (size_t)std::max(1, atoi(e));  // development
+        const size_t chunk = edit_chunk();
         std::vector<EpResult> res(tiles.size());
         const ChunkRun r{ctx, A, B, ts};
         for (size_t t0 = 0; t0 < tiles.size(); t0 += chunk)
@@ -271,7 +289,150 @@ int edit_paths_impl(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la *las, int64_t n
     return DH_OK;
 }
 
+// the records of [r0, r1) -- whole records, tiles [tile_off[r0], tile_off[r1]) -- through the edit-path kernels and
+// k_trace_transpose: their transposed trace pairs into set->trace, their diffs into set->la
+int transpose_chunk(const ChunkRun &r, const std::vector<EpTile> &tiles, const std::vector<int64_t> &tile_off,
+                    const std::vector<int64_t> &slot_off, int64_t r0, int64_t r1, std::vector<EpResult> &res, dh_edit_paths *tmp,
+                    dh_la_set *set)
+{
+    dh_ctx *ctx = r.ctx;
+    hipStream_t st = ctx->stream;
+    const uint8_t *d_ops = nullptr;
+    if (int rc = run_chunk(r, tiles, (size_t)tile_off[(size_t)r0], (size_t)tile_off[(size_t)r1], res, tmp, &d_ops)) return rc;
+    const size_t nrec = (size_t)(r1 - r0), nslots = (size_t)(slot_off[(size_t)r1] - slot_off[(size_t)r0]);
+    std::vector<EpTrRec> recs(nrec);
+    int64_t op = 0;
+    for (int64_t i = r0; i < r1; i++) {
+        dh_la &t = set->la[(size_t)i];
+        int64_t nops = 0, score = 0;
+        for (int64_t k = tile_off[(size_t)i]; k < tile_off[(size_t)i + 1]; k++) {
+            nops += res[(size_t)k].nops;
+            score += res[(size_t)k].score;
+        }
+        if (nops > INT32_MAX) return dh_fail(DH_EINVAL, "dh_la_transpose: a path of more than 2^31 ops");
+        t.diffs = (int32_t)score;
+        recs[(size_t)(i - r0)] = EpTrRec{op, slot_off[(size_t)i] - slot_off[(size_t)r0], (int32_t)nops,
+                                         (t.flags & DH_FLAG_COMP) ? 1 : 0, t.abpos, t.aepos};
+        op += nops;
+    }
+    if (!d_ops) return dh_fail(DH_EHIP, "dh_la_transpose: the chunk left no ops");  // (every record has B bases, hence ops)
+    EpTrRec *d_recs;
+    uint2 *d_bound;
+    uint32_t *d_pairs;
+    int32_t *d_status;
+    if (int rc = scr(ctx, 85, nrec, &d_recs)) return rc;
+    if (int rc = scr(ctx, 86, nslots, &d_bound)) return rc;
+    if (int rc = scr(ctx, 87, nslots, &d_pairs)) return rc;
+    if (int rc = scr(ctx, 88, nrec, &d_status)) return rc;
+    HIPCHK(hipMemcpyAsync(d_recs, recs.data(), sizeof(EpTrRec) * nrec, hipMemcpyHostToDevice, st));
+    dhk_trace_transpose(st, d_recs, (int32_t)nrec, d_ops, r.ts, d_bound, d_pairs, d_status);
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> status(nrec);
+    HIPCHK(hipMemcpyAsync(set->trace.data() + 2 * slot_off[(size_t)r0], d_pairs, sizeof(uint32_t) * nslots, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(status.data(), d_status, sizeof(int32_t) * nrec, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (size_t k = 0; k < nrec; k++) {
+        char msg[160];
+        if (status[k] & 2) {
+            snprintf(msg, sizeof(msg), "dh_la_transpose: LA %lld: the ops of its path do not span its B interval", (long long)(r0 + (int64_t)k));
+            return dh_fail(DH_EHIP, msg);
+        }
+        if (status[k] & 1) {
+            snprintf(msg, sizeof(msg), "dh_la_transpose: LA %lld: a tile of the transposed trace does not fit 16 bits", (long long)(r0 + (int64_t)k));
+            return dh_fail(DH_EOVERFLOW, msg);
+        }
+    }
+    return DH_OK;
+}
+
+int transpose_impl(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la *las, int64_t n, const uint16_t *trace, int64_t trace_len,
+                   int32_t ts, int32_t want_best, dh_la_set **out, int64_t *src_index)
+{
+    if (!ctx || !A || !B || !out || n < 0 || (n > 0 && (!las || !trace))) return dh_fail(DH_EINVAL, "dh_la_transpose: bad argument");
+    if (ts < 1 || ts > EP_TSPACE_MAX) return dh_fail(DH_EINVAL, "dh_la_transpose: tspace must be in [1, 250]");
+    *out = nullptr;
+    // ---- validation, tiling and the transposed coordinates on the host, before anything is launched
+    std::unique_ptr<dh_la_set> set(new dh_la_set);
+    set->tspace = ts;
+    set->device = ctx->device;
+    set->la.resize((size_t)n);
+    std::vector<EpTile> tiles;
+    std::vector<int64_t> tile_off((size_t)n + 1, 0), slot_off((size_t)n + 1, 0);
+    for (int64_t i = 0; i < n; i++) {
+        const dh_la &l = las[i];
+        if (int rc = cut_record(A, B, l, i, trace, trace_len, ts, tiles)) return rc;
+        tile_off[(size_t)i + 1] = (int64_t)tiles.size();
+        if (l.bepos == l.bbpos) {
+            char msg[128];
+            snprintf(msg, sizeof(msg), "dh_la_transpose: LA %lld: no B bases, the transposed record has no A interval", (long long)i);
+            return dh_fail(DH_EINVAL, msg);
+        }
+        const int32_t alen = (int32_t)(A->h_off[(size_t)l.aread + 1] - A->h_off[(size_t)l.aread]);
+        const int32_t blen = (int32_t)(B->h_off[(size_t)l.bread + 1] - B->h_off[(size_t)l.bread]);
+        const bool comp = (l.flags & DH_FLAG_COMP) != 0;
+        dh_la t;
+        memset(&t, 0, sizeof(t));
+        t.aread = l.bread;
+        t.bread = l.aread;
+        t.abpos = comp ? blen - l.bepos : l.bbpos;
+        t.aepos = comp ? blen - l.bbpos : l.bepos;
+        t.bbpos = comp ? alen - l.aepos : l.abpos;
+        t.bepos = comp ? alen - l.abpos : l.aepos;
+        t.flags = l.flags & ~(DH_FLAG_START | DH_FLAG_NEXT | DH_FLAG_BEST | DH_FLAG_DISABLED);
+        const int32_t nt = ep::tr_tiles(t.abpos, t.aepos, ts);
+        t.tlen = 2 * nt;
+        t.toff = 2 * slot_off[(size_t)i];
+        slot_off[(size_t)i + 1] = slot_off[(size_t)i] + nt;
+        set->la[(size_t)i] = t;
+    }
+    set->trace.resize((size_t)(2 * slot_off[(size_t)n]));
+    if (n > 0) {
+        HIPCHK(hipSetDevice(ctx->device));
+        if (int rc = dh_ensure_rc(B)) return rc;
+        // ---- chunks of whole records: DH_EDIT_CHUNK tiles at most, a larger record on its own
+        const int64_t chunk = (int64_t)edit_chunk();
+        std::vector<EpResult> res(tiles.size());
+        dh_edit_paths tmp;
+        const ChunkRun r{ctx, A, B, ts};
+        for (int64_t r0 = 0, r1; r0 < n; r0 = r1) {
+            r1 = r0 + 1;
+            while (r1 < n && tile_off[(size_t)r1 + 1] - tile_off[(size_t)r0] <= chunk) r1++;
+            if (int rc = transpose_chunk(r, tiles, tile_off, slot_off, r0, r1, res, &tmp, set.get())) return rc;
+        }
+    }
+    // ---- chain flags and LAsort order; records equal in every key of the order keep the order of their sources (toff
+    // ascends with the source index)
+    std::stable_sort(set->la.begin(), set->la.end(), dh_la_less);  // groups the records by aread
+    dh_finish_transposed_set(set.get(), want_best != 0, dh_ctx_near_best_ppm(ctx));
+    for (size_t i = 0, j; i < set->la.size(); i = j) {
+        for (j = i + 1; j < set->la.size() && !dh_la_less(set->la[i], set->la[j]); j++) {}
+        if (j - i > 1) std::sort(set->la.begin() + (int64_t)i, set->la.begin() + (int64_t)j, [](const dh_la &p, const dh_la &q) { return p.toff < q.toff; });
+    }
+    if (src_index)
+        for (size_t i = 0; i < set->la.size(); i++)
+            src_index[i] = (std::upper_bound(slot_off.begin(), slot_off.end(), set->la[i].toff / 2) - slot_off.begin()) - 1;
+    *out = set.release();
+    return DH_OK;
+}
+
 }  // namespace
+
+extern "C" int dh_la_transpose(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la *las, int64_t n, const uint16_t *trace,
+                               int32_t tspace, int32_t want_best, dh_la_set **out, int64_t *src_index)
+{
+    return transpose_impl(ctx, A, B, las, n, trace, -1, tspace, want_best, out, src_index);
+}
+
+extern "C" int dh_la_set_transpose(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la_set *set, int32_t want_best, dh_la_set **out,
+                                   int64_t *src_index)
+{
+    if (!set) return dh_fail(DH_EINVAL, "dh_la_set_transpose: set is NULL");
+    if (set->la.empty() && set->d_la_n > 0)
+        return dh_fail(DH_EINVAL, "dh_la_set_transpose: the records of this set were left on the device");
+    if (int rc = dh_la_set_ensure_host_trace(const_cast<dh_la_set *>(set))) return rc;
+    return transpose_impl(ctx, A, B, set->la.data(), (int64_t)set->la.size(), set->trace.data(), (int64_t)set->trace.size(),
+                          set->tspace, want_best, out, src_index);
+}
 
 extern "C" int dh_la_edit_paths(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la *las, int64_t n, const uint16_t *trace,
                                 int32_t tspace, int64_t first, int64_t count, dh_edit_paths **out)

@@ -57,6 +57,13 @@ struct EpCopy {               // k_edit_compact: where a tile's op words are and
     int32_t nops, general;    // general: the words are in the full-matrix kernel's buffer
 };
 
+struct EpTrRec {        // one record of a launch of k_trace_transpose
+    int64_t op0;        // its first op in the chunk's ops
+    int64_t slot0;      // its first tile among the tiles of the launch (boundary scratch and output pairs)
+    int32_t nops, comp;
+    int32_t a0, a1;     // abpos', aepos': the interval on the B read's forward strand
+};
+
 namespace ep {
 using namespace dhbv;
 
@@ -289,6 +296,62 @@ inline int tile_class(int32_t rl, int32_t ql, int32_t diffs)
     if (diffs < 0 || band > 63 || d >= band) return 0;
     return band <= 31 ? 1 : 2;
 }
+
+// ---- transposition of a record's path (k_trace_transpose): the ops of the transposed record are the record's own with
+// codes 1 and 2 exchanged, for a COMP record in reverse order.  Nothing is rewritten: the words below hold the codes as
+// k_edit_compact left them, in the order of the transposed path, and the counts read them with the roles exchanged.
+
+#define EP_TR_NONE 4u                          /* a byte behind the end of the path */
+#define EP_TR_LANE_OPS 64                      /* ops per lane and pass */
+#define EP_TR_PASS_OPS (64 * EP_TR_LANE_OPS)   /* ops per pass of a wavefront */
+
+// ops k .. k + 7 of the transposed path (k a multiple of 8), op k in the lowest byte
+EP_HD uint64_t tr_word(const uint8_t *ops, int32_t nops, int32_t comp, int32_t k)
+{
+    const int32_t lo = comp ? nops - 8 - k : k;  // the first of the eight in the record's own order
+    uint64_t w = 0;
+    if (lo >= 0 && lo + 8 <= nops) {
+        memcpy(&w, ops + lo, 8);
+    } else {
+        for (int u = 0; u < 8; u++) {
+            const int32_t x = lo + u;
+            w |= (uint64_t)((x >= 0 && x < nops) ? (uint32_t)ops[x] : EP_TR_NONE) << (8 * u);
+        }
+    }
+    return comp ? __builtin_bswap64(w) : w;
+}
+
+// adds what the ops of a word advance: a = bases of A' (every op but the record's code 1), b = bases of B' (every op but its
+// code 2), d = non-zero ops
+EP_HD void tr_count(uint64_t w, uint32_t &a, uint32_t &b, uint32_t &d)
+{
+    const uint64_t M = 0x0101010101010101ull;
+    const uint64_t lo = w & M, hi = (w >> 1) & M, valid = ~(w >> 2) & M;
+    a += (uint32_t)__builtin_popcountll(valid & ~(lo & ~hi));
+    b += (uint32_t)__builtin_popcountll(valid & ~(hi & ~lo));
+    d += (uint32_t)__builtin_popcountll(valid & (lo | hi));
+}
+
+// walk of the 64 ops of a lane's slice from position `pos` of A' with the running (b, d) at its start: at_grid(g, d, b)
+// right after every op that brings A' to a multiple g of ts
+template <typename F>
+EP_HD void tr_walk(const uint64_t (&w)[8], int32_t pos, int32_t ts, uint32_t b, uint32_t d, F &&at_grid)
+{
+    int32_t next = (pos / ts + 1) * ts;
+    for (int j = 0; j < 8; j++)
+        for (int u = 0; u < 8; u++) {
+            const uint32_t c = (uint32_t)(w[j] >> (8 * u)) & 0xFFu;
+            if (c & EP_TR_NONE) continue;
+            b += c != EP_OP_INS;
+            d += c != EP_OP_MATCH;
+            if (c == EP_OP_DEL || ++pos != next) continue;
+            at_grid(next, d, b);
+            next += ts;
+        }
+}
+
+// tiles of the transposed record: the grid points strictly inside (a0, a1), plus one (a1 > a0)
+EP_HD int32_t tr_tiles(int32_t a0, int32_t a1, int32_t ts) { return (a1 + ts - 1) / ts - a0 / ts; }
 
 }  // namespace ep
 

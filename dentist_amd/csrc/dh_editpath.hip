@@ -8,6 +8,9 @@
 //                     left neighbour resolved by a prefix minimum over the wavefront.  Any rl <= 250, ql <= 1000.
 //   k_edit_compact    the op words of a chunk's tiles (back to front, eight per word) to their place in the chunk's output,
 //                     front to back, one byte per op.
+//   k_trace_transpose one wavefront per record: from those ops, the running (diffs, bases) at every trace point of the
+//                     TRANSPOSED record, whose grid lies on the B read (dh_la_transpose); k_trace_pairs turns them into the
+//                     trace pairs.  The ops never leave the device.
 //
 // Where the decision words live: three planes of 64 NW bits per matrix row are up to 6 (NW = 1) / 12 KB (NW = 2) per tile
 // at tspace = 250.  In LDS that is 384 / 768 KB per wavefront of 64 tiles against 160 KB per CU -- even at tspace = 100 a
@@ -171,6 +174,99 @@ k_edit_compact(const EpCopy *__restrict__ cp, int32_t n, const uint64_t *__restr
         const uint64_t wv = ow[c.wbase + (int64_t)(q >> 3) * c.wstride];
         out[c.out + p] = (uint8_t)(wv >> (8 * (q & 7)));
     }
+}
+
+// inclusive sum over the 64 lanes: row_shr 1, 2, 4, 8 inside the rows of 16, then row_bcast:15 / row_bcast:31 (the
+// sequence dh_mjoin.hip's scans use)
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ uint32_t ep_dpp0(uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWMASK, 0xF, false);
+}
+__device__ __forceinline__ uint32_t ep_scan_add(uint32_t v)
+{
+    v += ep_dpp0<0x111, 0xF>(v);
+    v += ep_dpp0<0x112, 0xF>(v);
+    v += ep_dpp0<0x114, 0xF>(v);
+    v += ep_dpp0<0x118, 0xF>(v);
+    v += ep_dpp0<0x142, 0xA>(v);
+    v += ep_dpp0<0x143, 0xC>(v);
+    return v;
+}
+
+// One wavefront per record, passes of 64 lanes x 64 ops of the transposed path (dh_editpath.h: tr_word).  A lane counts
+// what its 64 ops advance, a scan over the wavefront and the wave-uniform carry of the passes before give the position at
+// the start of its slice, and the lane walks its ops only when a grid point of A' lies inside: at the op that reaches
+// grid point m it stores the running (diffs, B' bases) to bound[m - 1], i.e. the END of tile m - 1.  The op that reaches
+// a grid point is unique, so every slot has one writer; the last slot takes the totals.  status: 2 when the ops do not
+// advance A' by a1 - a0 (the host planned the tiles from that interval).
+__global__ void __launch_bounds__(64)
+k_trace_transpose(const EpTrRec *__restrict__ recs, int32_t n, const uint8_t *__restrict__ ops, int32_t ts,
+                  uint2 *__restrict__ bound, int32_t *__restrict__ status)
+{
+    const int32_t g = blockIdx.x, lane = threadIdx.x;
+    if (g >= n) return;
+    const EpTrRec r = recs[g];
+    const uint8_t *o = ops + r.op0;
+    const int32_t ntiles = ep::tr_tiles(r.a0, r.a1, ts), g0 = r.a0 / ts;
+    uint2 *bd = bound + r.slot0;
+    uint32_t ca = 0, cb = 0, cd = 0;  // what the passes before advanced: wave-uniform
+    for (int32_t p0 = 0; p0 < r.nops; p0 += EP_TR_PASS_OPS) {
+        const int32_t k0 = p0 + lane * EP_TR_LANE_OPS;
+        uint64_t w[8];
+        uint32_t sa = 0, sb = 0, sd = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            w[j] = k0 + 8 * j < r.nops ? ep::tr_word(o, r.nops, r.comp, k0 + 8 * j) : 0x0404040404040404ull;
+            ep::tr_count(w[j], sa, sb, sd);
+        }
+        const uint32_t iab = ep_scan_add(sa | (sb << 16));  // (a pass advances either sequence by 4096 at most)
+        const uint32_t id = ep_scan_add(sd);
+        const int32_t pos = r.a0 + (int32_t)(ca + (iab & 0xFFFFu) - sa), next = (pos / ts + 1) * ts;
+        if (next <= pos + (int32_t)sa && next < r.a1)
+            ep::tr_walk(w, pos, ts, cb + (iab >> 16) - sb, cd + id - sd, [&](int32_t gp, uint32_t d, uint32_t b) {
+                const int32_t m = gp / ts - g0 - 1;
+                if (gp < r.a1 && m >= 0 && m < ntiles - 1) bd[m] = make_uint2(d, b);
+            });
+        const uint32_t tab = (uint32_t)__builtin_amdgcn_readlane((int)iab, 63);
+        ca += tab & 0xFFFFu;
+        cb += tab >> 16;
+        cd += (uint32_t)__builtin_amdgcn_readlane((int)id, 63);
+    }
+    if (lane == 0) {
+        if (ntiles > 0) bd[ntiles - 1] = make_uint2(cd, cb);
+        status[g] = (int64_t)ca == (int64_t)r.a1 - r.a0 ? 0 : 2;
+    }
+}
+
+// pair m of a record = bound[m] - bound[m - 1], (diffs, B' bases) as two u16 in one 32-bit store: consecutive lanes write
+// consecutive words.  status |= 1 when a value does not fit.
+__global__ void __launch_bounds__(64)
+k_trace_pairs(const EpTrRec *__restrict__ recs, int32_t n, int32_t ts, const uint2 *__restrict__ bound,
+              uint32_t *__restrict__ pairs, int32_t *__restrict__ status)
+{
+    const int32_t g = blockIdx.x, lane = threadIdx.x;
+    if (g >= n) return;
+    const EpTrRec r = recs[g];
+    const int32_t ntiles = ep::tr_tiles(r.a0, r.a1, ts);
+    const uint2 *bd = bound + r.slot0;
+    bool over = false;
+    for (int32_t m = lane; m < ntiles; m += 64) {
+        const uint2 e = bd[m], s = m ? bd[m - 1] : make_uint2(0u, 0u);
+        const uint32_t d = e.x - s.x, b = e.y - s.y;
+        over |= d > 0xFFFFu || b > 0xFFFFu;
+        pairs[r.slot0 + m] = (d & 0xFFFFu) | (b << 16);
+    }
+    const bool any = __any(over);
+    if (lane == 0 && any) status[g] |= 1;
+}
+
+extern "C" void dhk_trace_transpose(hipStream_t st, const EpTrRec *recs, int32_t n, const uint8_t *ops, int32_t ts, uint2 *bound,
+                                    uint32_t *pairs, int32_t *status)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_trace_transpose, dim3((uint32_t)n), dim3(64), 0, st, recs, n, ops, ts, bound, status);
+    hipLaunchKernelGGL(k_trace_pairs, dim3((uint32_t)n), dim3(64), 0, st, recs, n, ts, bound, pairs, status);
 }
 
 extern "C" void dhk_edit_fast(hipStream_t st, int nw, const EpTile *tiles, int32_t n, const uint8_t *abases,

@@ -220,6 +220,12 @@ struct dh_la_set {
 };
 // the host copy of a set's trace values, downloaded on first use when they were left on the device
 int dh_la_set_ensure_host_trace(dh_la_set *s);
+// damapper -n of a context: its own value or the process default
+int32_t dh_ctx_near_best_ppm(const dh_ctx *ctx);
+// what dh_align_db_transposed and dh_la_transpose do last with their transposed records (aread = read, bread = contig;
+// grouped by aread): chain flags by select_best_range with the roles of the sequences exchanged, then LAsort order
+void dh_finish_transposed_set(dh_la_set *set, bool want_best, int32_t near_ppm);
+bool dh_la_less(const dh_la &p, const dh_la &q);  // LAsort order (base.d:1787-1809)
 
 // result of the process stage (dh_process.cpp; dh_comm.cpp assembles the gathered result of all ranks)
 struct dh_insertions {

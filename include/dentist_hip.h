@@ -706,6 +706,31 @@ int64_t dh_format_cigar(const uint8_t *ops, int64_t nops, int32_t extended, char
 int64_t dh_format_alignment(const uint8_t *a, const uint8_t *b, const uint8_t *ops, int64_t nops, int32_t width,
                             char *out, int64_t cap);
 
+/* ---- exact transposition of local alignments: the records `damapper -C` writes as <B>.<A>.las (dazzler.d:6158-6170,
+ *      getLasFile :4339-4354) for alignments that already exist -- the SAME alignments with the roles of the sequences
+ *      exchanged, not a second alignment of the transposed pair (dh_align_db_transposed).  Per record, from the ops of
+ *      dh_la_edit_paths:
+ *        aread', bread'     bread, aread
+ *        abpos', aepos'     bbpos, bepos           (COMP: blen - bepos, blen - bbpos)
+ *        bbpos', bepos'     abpos, aepos           (COMP: alen - aepos, alen - abpos)
+ *        path               the ops with codes 1 and 2 exchanged (COMP: in reverse order as well)
+ *        flags              COMP kept; START, NEXT, BEST and DISABLED cleared
+ *      The trace lies on the grid of A' (the B read on its forward strand): a tile ends right after the op that brings the
+ *      A' position to the next multiple of tspace strictly inside (abpos', aepos'), ops that follow it without advancing
+ *      A' belong to the next tile, the last tile takes the rest; a tile is (its non-zero ops, its ops that advance B').
+ *      tlen' = 2 x tiles; diffs' = the non-zero ops of the path = dh_edit_paths_score of the source record (it may be
+ *      smaller than the source's diffs).
+ *      out: a host-resident set of the same tspace with exactly n records in LAsort order (records equal in every key
+ *      keep the order of their sources); src_index[i] (n entries, or NULL) = index in las of the source of record i.
+ *      want_best != 0: chain flags as on the second set of dh_align_db_transposed (roles exchanged, the context's -n).
+ *      A and B may be the same DB.  DH_EINVAL, found on the host before anything is launched: whatever dh_la_edit_paths
+ *      refuses, and a record with bepos == bbpos (no A' interval).  DH_EOVERFLOW: a transposed tile whose diffs or bases
+ *      do not fit 16 bits (found on the device; dh_last_error names the record). */
+int dh_la_transpose(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la *las, int64_t n, const uint16_t *trace,
+                    int32_t tspace, int32_t want_best, dh_la_set **out, int64_t *src_index /* n entries or NULL */);
+int dh_la_set_transpose(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la_set *set, int32_t want_best,
+                        dh_la_set **out, int64_t *src_index);
+
 /* ---- gap-closed assembly writer (host only): the linear-scaffold subset of `dentist output`
  *      (source/dentist/commands/output.d:743-925): header "<id>\tscaffold-<first contig id>", contig
  *      slices lower case, insertions upper case (highlight != 0), unclosed gaps as 'n' runs, lines

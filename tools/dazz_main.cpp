@@ -24,6 +24,9 @@
 //   LApaf [-a] [-w<int(100)>] <A:db|dam> [<B:db|dam>] <align:las> [first-last]   base-level alignments of the records of a
 //                                    .las as PAF with an extended cigar (dh_la_edit_paths: getExactAlignment's per-trace-point
 //                                    part, dazzler.d:2405-2426); -a adds the alignment text (SequenceAlignment.toString)
+//   LAtranspose [-b] <A:db|dam> <B:db|dam> <in:las> <out:las>   the same alignments with the roles of the sequences exchanged
+//                                    (dh_la_transpose: the file `damapper -C` names <B>.<A>.las, dazzler.d:6158-6170, as the
+//                                    exact transposition of <in>); -b sets the chain flags
 // DENTIST only sees exit codes, files and stdout of these tools; flags it never emits are rejected.
 #include <algorithm>
 #include <cmath>
@@ -835,6 +838,54 @@ static int tool_lapaf(const std::vector<std::string> &args)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- LAtranspose
+static int tool_latranspose(const std::vector<std::string> &args)
+{
+    bool best = false;
+    std::vector<std::string> pos;
+    for (const std::string &a : args) {
+        if (a == "-b")
+            best = true;
+        else if (a[0] == '-')
+            die("unknown option " + a);
+        else
+            pos.push_back(a);
+    }
+    if (pos.size() != 4) die("usage: LAtranspose [-b] <A:db|dam> <B:db|dam> <in:las> <out:las>");
+    const bool two = pos[1] != pos[0];
+    Dev va = open_dev(pos[0]);
+    Dev vb;
+    if (two) {
+        vb.dz = open_dazz(pos[1]);
+        CHK(dh_db_create(va.ctx, dh_dazz_bases(vb.dz), dh_dazz_offsets(vb.dz), dh_dazz_nreads(vb.dz), nullptr, &vb.db));
+    }
+    const dh_dazz *da = va.dz, *dbz = two ? vb.dz : va.dz;
+    dh_db *A = va.db, *B = two ? vb.db : va.db;
+    dh_la_set *set = nullptr, *out = nullptr;
+    CHK(dh_las_read(pos[2].c_str(), &set));
+    const int64_t n = dh_la_set_count(set);
+    std::vector<dh_la> las(dh_la_set_records(set), dh_la_set_records(set) + n);
+    for (dh_la &l : las) {
+        l.aread -= dh_dazz_first_id(da);
+        l.bread -= dh_dazz_first_id(dbz);
+    }
+    CHK(dh_la_transpose(va.ctx, A, B, las.data(), n, dh_la_set_trace(set), dh_la_set_tspace(set), best ? 1 : 0, &out, nullptr));
+    las.assign(dh_la_set_records(out), dh_la_set_records(out) + dh_la_set_count(out));
+    for (dh_la &l : las) {  // (the id offsets exchanged with the reads)
+        l.aread += dh_dazz_first_id(dbz);
+        l.bread += dh_dazz_first_id(da);
+    }
+    CHK(dh_las_write(pos[3].c_str(), las.data(), (int64_t)las.size(), dh_la_set_trace(out), dh_la_set_tspace(out)));
+    dh_la_set_destroy(out);
+    dh_la_set_destroy(set);
+    if (two) {
+        dh_db_destroy(vb.db);
+        dh_dazz_close(vb.dz);
+    }
+    close_dev(va);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     g_tool = argv[0];
@@ -863,6 +914,7 @@ int main(int argc, char **argv)
     if (g_tool == "Catrack") return tool_catrack(args);
     if (g_tool == "TANmask") return tool_tanmask(args);
     if (g_tool == "LApaf") return tool_lapaf(args);
+    if (g_tool == "LAtranspose") return tool_latranspose(args);
     die("unknown tool (expected fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv "
         "computeintrinsicqv daccord merge-insertions)");
     return 1;
