@@ -335,8 +335,8 @@ static int all_gather_st(dh_comm *c, const uint8_t *payload, int64_t nbytes, int
     uint8_t *d_send = nullptr, *d_recv = nullptr;
     const size_t nstage = (size_t)std::max<int64_t>(std::max(nbytes, total), 1);
     uint8_t *stage = nullptr, *buf = nullptr;
-    int rc2 = dh_scratch(ctx, 56, (size_t)cap, (void **)&d_send);
-    if (!rc2) rc2 = dh_scratch(ctx, 57, (size_t)cap * (size_t)W, (void **)&d_recv);
+    int rc2 = dh_scratch(ctx, SLOT_COMM_SEND, (size_t)cap, (void **)&d_send);
+    if (!rc2) rc2 = dh_scratch(ctx, SLOT_COMM_RECV, (size_t)cap * (size_t)W, (void **)&d_recv);
     if (!rc2 && !(stage = (uint8_t *)dh_pinned_alloc(nstage))) rc2 = dh_fail(DH_ENOMEM, "dh_comm_all_gather: out of page-locked memory");
     if (!rc2 && !(buf = (uint8_t *)malloc((size_t)std::max<int64_t>(total, 1)))) rc2 = dh_fail(DH_ENOMEM, "dh_comm_all_gather: out of memory");
     struct Staged {
@@ -435,8 +435,8 @@ static int all_to_all_st(dh_comm *c, const uint8_t *const *per_dest, const int64
     // (2) the buffers, then the second status word
     uint8_t *d_send = nullptr, *d_recv = nullptr, *stage = nullptr, *buf = nullptr;
     const size_t nstage = (size_t)std::max<int64_t>(std::max(stot, rtot), 1);
-    int rc2 = dh_scratch(ctx, 56, (size_t)std::max<int64_t>(stot, 16), (void **)&d_send);
-    if (!rc2) rc2 = dh_scratch(ctx, 57, (size_t)std::max<int64_t>(rtot, 16), (void **)&d_recv);
+    int rc2 = dh_scratch(ctx, SLOT_COMM_SEND, (size_t)std::max<int64_t>(stot, 16), (void **)&d_send);
+    if (!rc2) rc2 = dh_scratch(ctx, SLOT_COMM_RECV, (size_t)std::max<int64_t>(rtot, 16), (void **)&d_recv);
     if (!rc2 && !(stage = (uint8_t *)dh_pinned_alloc(nstage))) rc2 = dh_fail(DH_ENOMEM, "dh_comm_all_to_all: out of page-locked memory");
     if (!rc2 && !(buf = (uint8_t *)malloc((size_t)std::max<int64_t>(rtot, 1)))) rc2 = dh_fail(DH_ENOMEM, "dh_comm_all_to_all: out of memory");
     struct Staged {

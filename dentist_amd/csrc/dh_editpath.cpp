@@ -4,11 +4,11 @@
 // A call validates every record against the two DBs, cuts the records into trace tiles and runs them chunk by chunk
 // (DH_EDIT_CHUNK tiles, a development knob): the tiles whose band fits a class go through k_edit_fast, the ones it does not
 // prove exact and the ones no class fits through k_edit_general, k_edit_compact puts the ops of the chunk in alignment
-// order, and the host appends them to the result.  Device scratch (arena slots 74..84) is bounded by the chunk.
+// order, and the host appends them to the result.  Device scratch (the SLOT_EP_* group) is bounded by the chunk.
 //
 // dh_la_transpose / dh_la_set_transpose run the same chunks cut between records, leave the ops of a chunk on the device
-// and let k_trace_transpose put the trace points of every record's transposed path on the grid of the B read (slots
-// 85..88); the host adds the coordinates, the chain flags and LAsort order.
+// and let k_trace_transpose put the trace points of every record's transposed path on the grid of the B read (the
+// SLOT_TR_* group); the host adds the coordinates, the chain flags and LAsort order.
 #include "dh_internal.h"
 
 #include <stdio.h>
@@ -50,7 +50,7 @@ namespace {
 #define EP_GENERAL_BATCH 2048 /* tiles per launch of the full-matrix kernel: 64 KB of decisions each at tspace = 250 */
 
 template <typename T>
-int scr(dh_ctx *ctx, int id, size_t count, T **out)
+int scr(dh_ctx *ctx, DhSlot id, size_t count, T **out)
 {
     return dh_scratch(ctx, id, sizeof(T) * std::max<size_t>(count, 1), (void **)out);
 }
@@ -123,7 +123,7 @@ struct ChunkRun {
 };
 
 // tiles [t0, t1) of `tiles` (alignment order): nops / score per tile into res[], the ops appended to out->ops -- or, with
-// keep_ops, left on the device (slot 84, tile after tile: a tile's first op is the sum of the nops before it) for a kernel
+// keep_ops, left on the device (SLOT_EP_OPS, tile after tile: a tile's first op is the sum of the nops before it) for a kernel
 // queued behind this call; *keep_ops is NULL when the chunk has no op
 int run_chunk(const ChunkRun &r, const std::vector<EpTile> &tiles, size_t t0, size_t t1, std::vector<EpResult> &res,
               dh_edit_paths *out, const uint8_t **keep_ops = nullptr)
@@ -158,10 +158,10 @@ int run_chunk(const ChunkRun &r, const std::vector<EpTile> &tiles, size_t t0, si
         EpTile *d_tiles;
         uint64_t *d_dm;
         EpResult *d_res;
-        if (int rc = scr(ctx, 74, nfast, &d_tiles)) return rc;
-        if (int rc = scr(ctx, 75, dm1 + dm2, &d_dm)) return rc;
-        if (int rc = scr(ctx, 76, wbase[2] + n2 * (size_t)owords[2], &d_ow)) return rc;
-        if (int rc = scr(ctx, 77, nfast, &d_res)) return rc;
+        if (int rc = scr(ctx, SLOT_EP_TILES, nfast, &d_tiles)) return rc;
+        if (int rc = scr(ctx, SLOT_EP_DM, dm1 + dm2, &d_dm)) return rc;
+        if (int rc = scr(ctx, SLOT_EP_OW, wbase[2] + n2 * (size_t)owords[2], &d_ow)) return rc;
+        if (int rc = scr(ctx, SLOT_EP_RES, nfast, &d_res)) return rc;
         HIPCHK(hipMemcpyAsync(d_tiles, stage.data(), sizeof(EpTile) * nfast, hipMemcpyHostToDevice, st));
         dhk_edit_fast(st, 1, d_tiles, (int32_t)n1, ab, bf, brc, rows[1], owords[1], d_dm, d_ow, d_res);
         dhk_edit_fast(st, 2, d_tiles + n1, (int32_t)n2, ab, bf, brc, rows[2], owords[2], d_dm + dm1, d_ow + wbase[2], d_res + n1);
@@ -202,11 +202,11 @@ int run_chunk(const ChunkRun &r, const std::vector<EpTile> &tiles, size_t t0, si
         int64_t *d_goff;
         uint32_t *d_dm;
         EpResult *d_res;
-        if (int rc = scr(ctx, 78, ng, &d_tiles)) return rc;
-        if (int rc = scr(ctx, 79, gb * (size_t)rows * 64, &d_dm)) return rc;
-        if (int rc = scr(ctx, 80, (size_t)goff[ng], &d_gow)) return rc;
-        if (int rc = scr(ctx, 81, ng + 1, &d_goff)) return rc;
-        if (int rc = scr(ctx, 83, ng, &d_res)) return rc;
+        if (int rc = scr(ctx, SLOT_EP_GEN_TILES, ng, &d_tiles)) return rc;
+        if (int rc = scr(ctx, SLOT_EP_GEN_DM, gb * (size_t)rows * 64, &d_dm)) return rc;
+        if (int rc = scr(ctx, SLOT_EP_GEN_OW, (size_t)goff[ng], &d_gow)) return rc;
+        if (int rc = scr(ctx, SLOT_EP_GEN_OFF, ng + 1, &d_goff)) return rc;
+        if (int rc = scr(ctx, SLOT_EP_GEN_RES, ng, &d_res)) return rc;
         HIPCHK(hipMemcpyAsync(d_tiles, stage.data(), sizeof(EpTile) * ng, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_goff, goff.data(), sizeof(int64_t) * (ng + 1), hipMemcpyHostToDevice, st));
         for (size_t g0 = 0; g0 < ng; g0 += gb)  // (one stream: a batch starts when the one before it is done with d_dm)
@@ -232,8 +232,8 @@ int run_chunk(const ChunkRun &r, const std::vector<EpTile> &tiles, size_t t0, si
     if (total == 0) return DH_OK;
     EpCopy *d_cp;
     uint8_t *d_out;
-    if (int rc = scr(ctx, 82, n, &d_cp)) return rc;
-    if (int rc = scr(ctx, 84, (size_t)total, &d_out)) return rc;
+    if (int rc = scr(ctx, SLOT_EP_COPY, n, &d_cp)) return rc;
+    if (int rc = scr(ctx, SLOT_EP_OPS, (size_t)total, &d_out)) return rc;
     HIPCHK(hipMemcpyAsync(d_cp, cp.data(), sizeof(EpCopy) * n, hipMemcpyHostToDevice, st));
     dhk_edit_compact(st, d_cp, (int32_t)n, d_ow, d_gow, d_out);
     HIPCHK(hipGetLastError());
@@ -320,10 +320,10 @@ int transpose_chunk(const ChunkRun &r, const std::vector<EpTile> &tiles, const s
     uint2 *d_bound;
     uint32_t *d_pairs;
     int32_t *d_status;
-    if (int rc = scr(ctx, 85, nrec, &d_recs)) return rc;
-    if (int rc = scr(ctx, 86, nslots, &d_bound)) return rc;
-    if (int rc = scr(ctx, 87, nslots, &d_pairs)) return rc;
-    if (int rc = scr(ctx, 88, nrec, &d_status)) return rc;
+    if (int rc = scr(ctx, SLOT_TR_RECS, nrec, &d_recs)) return rc;
+    if (int rc = scr(ctx, SLOT_TR_BOUND, nslots, &d_bound)) return rc;
+    if (int rc = scr(ctx, SLOT_TR_PAIRS, nslots, &d_pairs)) return rc;
+    if (int rc = scr(ctx, SLOT_TR_STATUS, nrec, &d_status)) return rc;
     HIPCHK(hipMemcpyAsync(d_recs, recs.data(), sizeof(EpTrRec) * nrec, hipMemcpyHostToDevice, st));
     dhk_trace_transpose(st, d_recs, (int32_t)nrec, d_ops, r.ts, d_bound, d_pairs, d_status);
     HIPCHK(hipGetLastError());

@@ -71,6 +71,59 @@ int dh_alloc_bases(hipStream_t st, int64_t total, uint8_t **alloc, uint8_t **bas
             return dh_fail(DH_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
     } while (0)
 
+// The slots of a context's scratch arena (dh_ctx::arena, dh_scratch): one enumerator per device buffer, named after what
+// it holds, grouped by the entry point that owns it.  A slot is one grow-only buffer.  A few slots are requested at
+// several sites by design (marked "several requests" below): every request is the same buffer and the largest request
+// wins -- a request that grows the buffer synchronises the stream and drops what it held, so such sites never need each
+// other's contents.  Groups do not share buffers, so an entry point never overwrites what another one left on the context.
+enum DhSlot : int {
+    // words shared by an alignment call and the 2-bit packers (several requests, all of DH_STW_COUNT words): DH_STW_* below
+    SLOT_STATUS,
+    // dh_align_db* / dh_map_reads (dh_align.cpp: alloc_scratch and the chunk stages): live for one call, rewritten by
+    // every chunk; the compacted records and trace values of the last chunk stay valid until the next alignment call
+    // (dh_la_set.d_trace / d_la / d_item_off point into SLOT_TROUT, SLOT_LAOUT, SLOT_NLA).  Several requests: SLOT_LA and
+    // SLOT_TRSLOTS (alloc_scratch, or extend_chunk once a symmetric launch has counted its candidates), SLOT_FSCR (one per
+    // seed tier, sized by the tier), SLOT_UNITS (one per kind of unit)
+    SLOT_CAND, SLOT_NCAND, SLOT_NHITS, SLOT_NLA, SLOT_NTR, SLOT_POOL, SLOT_CDJ, SLOT_QUEUE, SLOT_LA, SLOT_TRSLOTS,
+    SLOT_COUNTERS, SLOT_SUMS, SLOT_SUMMARY, SLOT_OVF, SLOT_REGS, SLOT_COLD, SLOT_LAOUT, SLOT_TROUT,
+    SLOT_FSCR, SLOT_MID_LIST, SLOT_BIG_LIST, SLOT_BIG_HITS,            // seed tiers: slab scratch, the reads of a tier, HBM-staged hits
+    SLOT_UNITS, SLOT_CANDOFF, SLOT_RECLIST, SLOT_RECCUR,               // symmetric launches (skip_self 2)
+    // the transposed file of dh_align_db_transposed: same life as the group above
+    SLOT_LA2, SLOT_TRSLOTS2, SLOT_NLA2, SLOT_NTR2, SLOT_A_PLANES, SLOT_A_RC_PLANES, SLOT_B_PK2, SLOT_B_RC_PK2, SLOT_LAOUT2,
+    SLOT_TROUT2,
+    // the per-chunk copies of B (chunk_copies, dh_align.cpp): made at the start of a chunk, read by its extension
+    SLOT_CHUNK_RC, SLOT_CHUNK_PK, SLOT_CHUNK_RCPK,
+    // the pile-up join (build_join, dh_align.cpp): built once per call, read by the seeds of every chunk
+    SLOT_JOIN_BLOB, SLOT_JOIN_PSUB, SLOT_JOIN_ENTRIES, SLOT_JOIN_SEGTAB, SLOT_JOIN_CURSOR, SLOT_JOIN_HITS,
+    // the mapping join (plan_mj_chunk, dh_align.cpp): planned per chunk, read by that chunk's seeds
+    SLOT_MJ_ENT, SLOT_MJ_SEGOFF, SLOT_MJ_TILE_N, SLOT_MJ_TILE_R, SLOT_MJ_SEG, SLOT_MJ_HSEG, SLOT_MJ_HITS, SLOT_MJ_RHITS,
+    SLOT_MJ_SEGTAB, SLOT_MJ_CTR,
+    // the process rounds (the vote and emit pass of a consensus round, dh_process.cpp): live for one round
+    SLOT_PR_VOFF, SLOT_PR_VOTES, SLOT_PR_OUT, SLOT_PR_STATUS, SLOT_PR_STAGE, SLOT_PR_SEGS, SLOT_PR_DECISIONS, SLOT_PR_CDIFF,
+    // comm (dh_comm.cpp: the staging buffers of a collective): live for one collective; several requests (one per kind)
+    SLOT_COMM_SEND, SLOT_COMM_RECV,
+    // edit paths (run_chunk, dh_editpath.cpp): live for one chunk of tiles; SLOT_EP_OPS is read by the transposition
+    SLOT_EP_TILES, SLOT_EP_DM, SLOT_EP_OW, SLOT_EP_RES, SLOT_EP_GEN_TILES, SLOT_EP_GEN_DM, SLOT_EP_GEN_OW, SLOT_EP_GEN_OFF,
+    SLOT_EP_GEN_RES, SLOT_EP_COPY, SLOT_EP_OPS,
+    // transpose (transpose_chunk, dh_editpath.cpp): live for one chunk of records, behind the edit paths of that chunk
+    SLOT_TR_RECS, SLOT_TR_BOUND, SLOT_TR_PAIRS, SLOT_TR_STATUS,
+    DH_SLOT_COUNT
+};
+// The words of SLOT_STATUS (DH_STW_COUNT x int32), one buffer with three users.  All of them run on the context's stream:
+//   DH_STW_STATUS   the DH_ST_* bits of an alignment call.  Written: cleared by alloc_scratch and by build_join (hit buffer
+//                   retry, fall-back to the directory), rewritten from the host by seed_chunk (a chunk that runs again),
+//                   ORed into by the join, mapping-join, seed, wave and tile kernels.  Read: build_join, seed_chunk,
+//                   gather_chunk.
+//   DH_STW_PACK     "a code outside 0..3 was met" of a forward packing.  Cleared, written (k_pack2, k_pack2_planes) and read
+//                   back by dh_ensure_packed (a DB's own copy) and by chunk_copies (a chunk's copy); both synchronise the
+//                   stream before they return, and neither runs while the other does.
+//   DH_STW_PACK_RC  the same flag of dh_ensure_packed's packing of the reverse complement: written by k_pack2, read by
+//                   nobody (the forward pass has decided); chunk_copies clears it along with DH_STW_PACK.
+// The fourth word is unused.  No word has two writers in flight at once: the packers run before alloc_scratch or between
+// two chunks' kernels of the same stream, and they never touch DH_STW_STATUS.
+enum { DH_STW_STATUS = 0, DH_STW_PACK = 1, DH_STW_PACK_RC = 2, DH_STW_COUNT = 4 };
+static_assert(DH_STW_PACK_RC == DH_STW_PACK + 1, "chunk_copies clears the two flag words with one memset");
+
 struct dh_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -95,10 +148,10 @@ struct dh_ctx {
     struct Arena {
         void *p = nullptr;
         size_t cap = 0;
-    } arena[96];
+    } arena[DH_SLOT_COUNT];
 };
 // slot `id` of the context's scratch arena, at least `bytes` large
-int dh_scratch(dh_ctx *ctx, int id, size_t bytes, void **out);
+int dh_scratch(dh_ctx *ctx, DhSlot id, size_t bytes, void **out);
 // per-sequence flags of a symmetric all-vs-all (DbView::pflags); NULL clears them
 int dh_db_set_pflags(struct dh_db *db, const uint8_t *flags);
 
@@ -223,9 +276,13 @@ int dh_la_set_ensure_host_trace(dh_la_set *s);
 // damapper -n of a context: its own value or the process default
 int32_t dh_ctx_near_best_ppm(const dh_ctx *ctx);
 // what dh_align_db_transposed and dh_la_transpose do last with their transposed records (aread = read, bread = contig;
-// grouped by aread): chain flags by select_best_range with the roles of the sequences exchanged, then LAsort order
+// grouped by aread): chain flags by dh_select_best_range with the roles of the sequences exchanged, then LAsort order
 void dh_finish_transposed_set(dh_la_set *set, bool want_best, int32_t near_ppm);
 bool dh_la_less(const dh_la &p, const dh_la &q);  // LAsort order (base.d:1787-1809)
+// damapper's chain flags (START / NEXT / BEST, DISABLED below near_ppm) of records grouped by bread (dh_laset.cpp)
+void dh_select_best_range(dh_la *la, size_t nla, int32_t near_ppm);
+// LAsort order of a B-major list of records over `na` A reads, in O(n)
+void dh_lasort(dh_la_set *res, int32_t na);
 
 // result of the process stage (dh_process.cpp; dh_comm.cpp assembles the gathered result of all ranks)
 struct dh_insertions {
@@ -284,6 +341,9 @@ void dh_mask_free(dh_db *db);
 // DBdust: ORs the low-complexity mask (k_dust) into the DB's mask bitmap; drops the cached index
 int dh_db_dust_impl(dh_db *db);
 int dh_ensure_packed(dh_db *db, bool with_rc);
+// the k-mer index of A (cached with the DB); light: the virtual axis only, for the calls whose hits come from the pile-up join
+int dh_build_index(dh_db *A, int32_t k, int32_t sepv, int32_t kmer_mod, bool light = false);
+int32_t dh_ceil_log2(uint64_t x);
 // dh_align_db with the final LAsort made optional (internal callers regroup on their own): want_sorted bit 0 = LAsort,
 // bit 1 = leave the trace values on the device (dh_la_set.d_trace / d_trace_len) when the call is one chunk
 int dh_align_db_ex(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_align_opts *opts, int32_t want_best,

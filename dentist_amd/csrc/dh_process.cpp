@@ -1033,21 +1033,21 @@ static int consensus_round(dh_ctx *ctx, dh_db *T, dh_db *R, const LaVec &las,
         voff[(size_t)t + 1] = voff[(size_t)t] + len + 1;
         ooff[(size_t)t + 1] = ooff[(size_t)t] + len * (1 + 2 * MAXINS) + 8;
     }
-    // big per-round buffers come from the context's grow-only scratch arena (slots 17..23)
+    // big per-round buffers come from the context's grow-only scratch arena (the SLOT_PR_* group)
     struct { int64_t *p; } d_voff, d_ooff;
     struct { uint32_t *p; } d_votes;
     struct { uint8_t *p; } d_out, d_stage, d_cnt;
     struct { int32_t *p; } d_status, d_outlen, d_coltmpl;
 #define SCRP(id, buf, count)                                                                     \
     if (int rc_ = dh_scratch(ctx, id, sizeof(*buf.p) * std::max<size_t>((size_t)(count), 1), (void **)&buf.p)) return rc_;
-    SCRP(17, d_voff, voff.size() + ooff.size())
+    SCRP(SLOT_PR_VOFF, d_voff, voff.size() + ooff.size())
     d_ooff.p = d_voff.p + voff.size();
-    SCRP(18, d_votes, (size_t)voff.back() * VSTRIDE)
-    SCRP(19, d_out, (size_t)ooff.back())
-    SCRP(20, d_status, 2 + (size_t)nt + (size_t)voff.back())
+    SCRP(SLOT_PR_VOTES, d_votes, (size_t)voff.back() * VSTRIDE)
+    SCRP(SLOT_PR_OUT, d_out, (size_t)ooff.back())
+    SCRP(SLOT_PR_STATUS, d_status, 2 + (size_t)nt + (size_t)voff.back())
     d_outlen.p = d_status.p + 2;
     d_coltmpl.p = d_outlen.p + nt;
-    SCRP(21, d_stage, (size_t)voff.back() * (2 + 2 * MAXINS))
+    SCRP(SLOT_PR_STAGE, d_stage, (size_t)voff.back() * (2 + 2 * MAXINS))
     d_cnt.p = d_stage.p + (size_t)voff.back() * (1 + 2 * MAXINS);
     HIPCHK(hipMemcpyAsync(d_voff.p, voff.data(), sizeof(int64_t) * voff.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_ooff.p, ooff.data(), sizeof(int64_t) * ooff.size(), hipMemcpyHostToDevice, st));
@@ -1056,7 +1056,7 @@ static int consensus_round(dh_ctx *ctx, dh_db *T, dh_db *R, const LaVec &las,
     // sparse votes: cover difference array and "other code" counts per column, scan partial sums
     const size_t ncolp = (size_t)voff.back() + 2;
     struct { uint32_t *p; } d_cdiff;
-    SCRP(25, d_cdiff, 2 * ncolp + ncolp / 2048 + 8)
+    SCRP(SLOT_PR_CDIFF, d_cdiff, 2 * ncolp + ncolp / 2048 + 8)
     uint32_t *d_vother = d_cdiff.p + ncolp, *d_csums = d_vother + ncolp;
     HIPCHK(dhk_memset(st, d_cdiff.p, 0, sizeof(uint32_t) * 2 * ncolp));
     if (int rc = dh_ensure_rc(R)) return rc;
@@ -1073,8 +1073,8 @@ static int consensus_round(dh_ctx *ctx, dh_db *T, dh_db *R, const LaVec &las,
             const int32_t cnt = (int32_t)std::min<size_t>((size_t)max_dp, c1 - s0);
             struct { SegDescH *p; } ds;
             struct { uint8_t *p; } fm, ob;
-            SCRP(22, ds, (size_t)cnt)
-            SCRP(23, fm, (size_t)cnt * (size_t)(ts + 1) * mrow + (size_t)cnt * 2 * SEG_MAX + (size_t)cnt * 2 + 32)
+            SCRP(SLOT_PR_SEGS, ds, (size_t)cnt)
+            SCRP(SLOT_PR_DECISIONS, fm, (size_t)cnt * (size_t)(ts + 1) * mrow + (size_t)cnt * 2 * SEG_MAX + (size_t)cnt * 2 + 32)
             ob.p = fm.p + (((size_t)cnt * (size_t)(ts + 1) * mrow + 7) & ~(size_t)7);  // op words: 8 ops each, 8-byte aligned
             uint16_t *d_nops = (uint16_t *)(ob.p + (((size_t)cnt * 2 * SEG_MAX + 7) & ~(size_t)7));
             HIPCHK(hipMemcpyAsync(ds.p, segs.data() + s0, sizeof(SegDescH) * (size_t)cnt, hipMemcpyHostToDevice, st));
