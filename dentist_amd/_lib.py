@@ -98,6 +98,7 @@ SYMBOLS = [
     "dh_la_edit_paths", "dh_la_set_edit_paths", "dh_edit_paths_destroy", "dh_edit_paths_count", "dh_edit_paths_op_off",
     "dh_edit_paths_ops", "dh_edit_paths_score", "dh_edit_paths_tile_off", "dh_edit_paths_tile_score",
     "dh_edit_paths_general_tiles", "dh_format_cigar", "dh_format_alignment", "dh_la_transpose", "dh_la_set_transpose",
+    "dh_nw_batch",
 ]
 
 _LIB = None
@@ -224,6 +225,7 @@ def lib():
     L.dh_format_cigar.restype = i64
     L.dh_format_alignment.argtypes = [vp, vp, vp, i64, i32, vp, i64]
     L.dh_format_alignment.restype = i64
+    L.dh_nw_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, ctypes.POINTER(vp), vp]
     _LIB = L
     return L
 
@@ -391,6 +393,31 @@ class Context:
                                       int(count), ctypes.byref(h)))
         return EditPaths(h)
 
+    def nw_batch(self, refs, qrys, free_shift=False):
+        """dh_nw_batch: the global alignment (findAlignment, indel penalty 1) of refs[i] against qrys[i] for every i; the
+        sequences are strings or base-code arrays, compared byte by byte.  Returns (EditPaths, status): ops and score
+        per pair as for Context.edit_paths (no tiles); status[i] is NW_OK or NW_BAND_EXCEEDED (score -1, no ops)."""
+        if len(refs) != len(qrys):
+            raise ValueError("refs and qrys differ in length")
+        r, roff = _concat_seqs(refs)
+        q, qoff = _concat_seqs(qrys)
+        return self.nw_batch_raw(r, roff, q, qoff, free_shift)
+
+    def nw_batch_raw(self, ref, ref_off, qry, qry_off, free_shift=False):
+        """nw_batch on concatenated sequences: pair i is ref[ref_off[i]:ref_off[i + 1]] against qry[qry_off[i]:qry_off[i + 1]]."""
+        r, q = np.ascontiguousarray(ref, dtype=np.uint8), np.ascontiguousarray(qry, dtype=np.uint8)
+        roff, qoff = np.ascontiguousarray(ref_off, dtype=np.int64), np.ascontiguousarray(qry_off, dtype=np.int64)
+        if len(roff) != len(qoff) or len(roff) < 1:
+            raise ValueError("ref_off and qry_off need n + 1 entries each")
+        n = len(roff) - 1
+        if n and (int(roff.max()) > len(r) or int(qoff.max()) > len(q)):
+            raise ValueError("an offset lies behind the end of the sequences")
+        status = np.zeros(n, dtype=np.int32)
+        h = ctypes.c_void_p()
+        _check(lib().dh_nw_batch(self._h, r.ctypes.data, roff.ctypes.data, q.ctypes.data, qoff.ctypes.data, n, int(bool(free_shift)),
+                                 ctypes.byref(h), status.ctypes.data))
+        return EditPaths(h), status
+
     def transpose(self, A, B, las, trace=None, tspace=None, select_best=False):
         """dh_la_transpose: the same alignments with the roles of the sequences exchanged (aread = B read, trace points on
         the B read's grid), from their edit paths.  Returns (las', trace', src_index), LAsort order; src_index[i] is the
@@ -470,6 +497,18 @@ def format_cigar(ops, extended=True):
     """dh_format_cigar: runs of = X I D (extended) or M I D of an op array of Context.edit_paths."""
     o = np.ascontiguousarray(ops, dtype=np.uint8)
     return _format(lib().dh_format_cigar, o.ctypes.data, len(o), int(bool(extended)))
+
+
+NW_OK, NW_BAND_EXCEEDED = 0, 1
+NW_MAX_LEN, NW_MAX_BAND = 65536, 4096
+
+
+def _concat_seqs(seqs):
+    arrs = [_seq_bytes(x) for x in seqs]
+    off = np.zeros(len(arrs) + 1, dtype=np.int64)
+    if arrs:
+        off[1:] = np.cumsum([len(a) for a in arrs])
+    return (np.concatenate(arrs) if arrs else np.zeros(0, np.uint8)), off
 
 
 def _seq_bytes(x):

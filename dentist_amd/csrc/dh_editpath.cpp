@@ -28,14 +28,6 @@ extern "C" void dhk_edit_compact(hipStream_t st, const EpCopy *cp, int32_t n, co
 extern "C" void dhk_trace_transpose(hipStream_t st, const EpTrRec *recs, int32_t n, const uint8_t *ops, int32_t ts, uint2 *bound,
                                     uint32_t *pairs, int32_t *status);
 
-struct dh_edit_paths {
-    std::vector<int64_t> op_off{0}, tile_off{0};
-    std::vector<uint8_t> ops;
-    std::vector<int32_t> score;
-    std::vector<uint16_t> tile_score;
-    int64_t general_tiles = 0;
-};
-
 extern "C" void dh_edit_paths_destroy(dh_edit_paths *p) { delete p; }
 extern "C" int64_t dh_edit_paths_count(const dh_edit_paths *p) { return p ? (int64_t)p->score.size() : 0; }
 extern "C" const int64_t *dh_edit_paths_op_off(const dh_edit_paths *p) { return p ? p->op_off.data() : nullptr; }

@@ -107,6 +107,9 @@ enum DhSlot : int {
     SLOT_EP_GEN_RES, SLOT_EP_COPY, SLOT_EP_OPS,
     // transpose (transpose_chunk, dh_editpath.cpp): live for one chunk of records, behind the edit paths of that chunk
     SLOT_TR_RECS, SLOT_TR_BOUND, SLOT_TR_PAIRS, SLOT_TR_STATUS,
+    // global alignment (run_launch, dh_nw.cpp): live for one launch group of pairs; SLOT_NW_REF / SLOT_NW_QRY hold the
+    // sequences of a chunk for all its launches
+    SLOT_NW_REF, SLOT_NW_QRY, SLOT_NW_PAIRS, SLOT_NW_DM, SLOT_NW_OW, SLOT_NW_RES, SLOT_NW_COPY, SLOT_NW_OPS,
     DH_SLOT_COUNT
 };
 // The words of SLOT_STATUS (DH_STW_COUNT x int32), one buffer with three users.  All of them run on the context's stream:
@@ -314,6 +317,15 @@ inline bool dh_continues_chain(const dh_la &prev, const dh_la &cur)
     return (cur.flags & DH_FLAG_NEXT) && !(cur.flags & DH_FLAG_START) && cur.aread == prev.aread && cur.bread == prev.bread &&
            (cur.flags & DH_FLAG_COMP) == (prev.flags & DH_FLAG_COMP);
 }
+
+// result of dh_la_edit_paths / dh_la_set_edit_paths (dh_editpath.cpp) and of dh_nw_batch (dh_nw.cpp)
+struct dh_edit_paths {
+    std::vector<int64_t> op_off{0}, tile_off{0};
+    std::vector<uint8_t> ops;
+    std::vector<int32_t> score;
+    std::vector<uint16_t> tile_score;
+    int64_t general_tiles = 0;
+};
 
 void dh_pileups_shift(dh_pileups *p, int32_t by);
 int dh_pileups_concat(dh_pileups *const *parts, int32_t nparts, dh_pileups **out);

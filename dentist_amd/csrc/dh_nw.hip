@@ -1,0 +1,126 @@
+// dh_nw.hip -- global alignment of whole sequence pairs (findAlignment, util/string.d:478-520, 775-831).  gfx950, wave64.
+//
+//   k_nw<CPL, NS>   one wavefront per pair: the diagonals [lo, hi] of the matrix, a matrix row per step, CPL band cells per
+//                   lane and strip, NS strips (dh_nw.h has the recurrence, the decisions and the exactness argument).  Row
+//                   i - 1 stays in registers; the one value a lane needs from its right neighbour comes by a shuffle, the
+//                   prefix minimum by DPP, the carry between strips by readlane.  No LDS.  Lane 0 walks the decisions back
+//                   and leaves the ops as the back-to-front words k_edit_compact (dh_editpath.hip) consumes.
+//
+// The decision words (2 bits per cell, [row][word]) live in global memory for the reason dh_editpath.hip gives: a 6 kb
+// pair at 129 diagonals is 200 KB.  The host bounds the footprint by the pairs it hands to a launch (DH_NW_CHUNK_KB).
+#include <hip/hip_runtime.h>
+
+#include "dh_nw.h"
+
+// inclusive prefix minimum over the 64 lanes: row_shr 1, 2, 4, 8 inside the rows of 16, then row_bcast:15 / row_bcast:31
+// (the sequence of ep_scan_add); a lane without a source keeps its own value
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ int32_t nw_dpp_min(int32_t v)
+{
+    const int32_t o = __builtin_amdgcn_update_dpp(v, v, CTRL, ROWMASK, 0xF, false);
+    return v < o ? v : o;
+}
+__device__ __forceinline__ int32_t nw_scan_min(int32_t v)
+{
+    v = nw_dpp_min<0x111, 0xF>(v);
+    v = nw_dpp_min<0x112, 0xF>(v);
+    v = nw_dpp_min<0x114, 0xF>(v);
+    v = nw_dpp_min<0x118, 0xF>(v);
+    v = nw_dpp_min<0x142, 0xA>(v);
+    v = nw_dpp_min<0x143, 0xC>(v);
+    return v;
+}
+
+template <int CPL, int NS>
+__global__ void __launch_bounds__(64)
+k_nw(const NwPair *__restrict__ pairs, int32_t n, const uint8_t *__restrict__ refs, const uint8_t *__restrict__ qrys,
+     int32_t free_shift, uint32_t *__restrict__ dmat, int64_t dm_words, uint64_t *__restrict__ owords, int64_t ow_words,
+     EpResult *__restrict__ res)
+{
+    constexpr int STRIP = 64 * CPL;
+    const int32_t g = blockIdx.x, lane = threadIdx.x;
+    if (g >= n) return;
+    const NwPair p = pairs[g];
+    const int32_t rl = p.rl, ql = p.ql, lo = p.lo, W = p.hi - p.lo + 1;
+    const int64_t stride = nw::row_words<CPL>(W);
+    // (the host planned the buffers from these very numbers: the test keeps a wrong plan from becoming a wild store)
+    if (rl < 1 || ql < 1 || rl > NW_MAX_LEN || ql > NW_MAX_LEN || W < 1 || W > NS * STRIP || lo < -rl || p.hi > ql ||
+        ql - rl < lo || ql - rl > p.hi || p.dm_off < 0 || p.dm_off + (int64_t)rl * stride > dm_words || p.ow_off < 0 ||
+        p.ow_off + (((int64_t)rl + ql + 7) >> 3) > ow_words) {
+        if (lane == 0) res[g] = EpResult{EP_REJECTED, 0u};
+        return;
+    }
+    const uint8_t *ref = refs + p.roff, *qry = qrys + p.qoff;
+    uint32_t *dm = dmat + p.dm_off;
+    int32_t prev[NS][CPL];
+    uint32_t qn[NS][CPL / 4];  // the query window of the next row
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+        const int32_t R0 = s * STRIP + lane * CPL;
+        nw::row0<CPL>(prev[s], lo + R0, nw::valid_limit(lo + R0, R0, W, ql), free_shift);
+        nw::load_window<CPL>(qry, lo + R0, ql, qn[s]);
+    }
+    uint64_t refw = 0;
+    for (int32_t i = 1; i <= rl; i++) {
+        const int32_t o = (i - 1) & 7;
+        if (o == 0) memcpy(&refw, ref + (i - 1), 8);
+        const uint32_t rc = (uint32_t)(refw >> (8 * o)) & 0xFFu;
+        const int32_t border = free_shift ? 0 : i;
+        // row i - 1 of the cell behind a lane's cells: the first cell of the lane to the right, for lane 63 the first
+        // cell of lane 0 of the next strip.  All of them before any strip overwrites its row.
+        int32_t nxt[NS];
+        uint32_t qc[NS][CPL / 4];
+#pragma unroll
+        for (int s = 0; s < NS; s++) {
+            nxt[s] = __shfl_down(prev[s][0], 1, 64);
+            const int32_t wrap = s + 1 < NS ? __builtin_amdgcn_readlane(prev[s + 1 < NS ? s + 1 : s][0], 0) : NW_INF;
+            if (lane == 63) nxt[s] = wrap;
+#pragma unroll
+            for (int k = 0; k < CPL / 4; k++) qc[s][k] = qn[s][k];
+            nw::load_window<CPL>(qry, i + lo + s * STRIP + lane * CPL, ql, qn[s]);  // row i + 1: j - 1 = i + lo + R
+        }
+        int32_t carry = NW_INF;  // min of (G - R) over the strips in front: wave-uniform
+#pragma unroll
+        for (int s = 0; s < NS; s++) {
+            const int32_t R0 = s * STRIP + lane * CPL, j0 = i + lo + R0;
+            const uint32_t ulim = nw::valid_limit(j0, R0, W, ql);
+            int32_t loc[CPL];
+            uint32_t mmbits;
+            const int32_t m = nw::row_min<CPL>(prev[s], nxt[s], rc, qc[s], j0, R0, ulim, border, loc, mmbits);
+            const int32_t incl = nw_scan_min(m);
+            int32_t excl = __shfl_up(incl, 1, 64);
+            excl = lane == 0 ? NW_INF : excl;
+            excl = excl < carry ? excl : carry;
+            const uint32_t word = nw::row_finish<CPL>(prev[s], nxt[s], loc, mmbits, excl, j0, R0, ulim);
+            if (R0 < W) dm[(int64_t)(i - 1) * stride + (R0 / CPL)] = word;
+            if (s + 1 < NS) {
+                const int32_t last = __builtin_amdgcn_readlane(incl, 63);
+                carry = carry < last ? carry : last;
+            }
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (lane != 0) return;
+    res[g] = nw::traceback<CPL>(rl, ql, lo, W, free_shift, dm, owords + p.ow_off);
+}
+
+extern "C" void dhk_nw(hipStream_t st, int cpl, int ns, const NwPair *pairs, int32_t n, const uint8_t *refs, const uint8_t *qrys,
+                       int32_t free_shift, uint32_t *dm, int64_t dm_words, uint64_t *ow, int64_t ow_words, EpResult *res)
+{
+    if (n <= 0) return;
+    const dim3 grid((uint32_t)n), block(64);
+#define NW_LAUNCH(C, S) \
+    hipLaunchKernelGGL((k_nw<C, S>), grid, block, 0, st, pairs, n, refs, qrys, free_shift, dm, dm_words, ow, ow_words, res)
+    if (cpl == 4 && ns == 1)
+        NW_LAUNCH(4, 1);
+    else if (cpl == 8 && ns == 1)
+        NW_LAUNCH(8, 1);
+    else if (cpl == 16 && ns == 1)
+        NW_LAUNCH(16, 1);
+    else if (cpl == 16 && ns == 2)
+        NW_LAUNCH(16, 2);
+    else if (cpl == 16 && ns == 4)
+        NW_LAUNCH(16, 4);
+#undef NW_LAUNCH
+}

@@ -731,6 +731,28 @@ int dh_la_transpose(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la *las, int64_t n
 int dh_la_set_transpose(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la_set *set, int32_t want_best,
                         dh_la_set **out, int64_t *src_index);
 
+/* ---- global alignment of arbitrary sequence pairs: findAlignment(reference, query, indelPenalty = 1, freeShift)
+ *      with its traceback (util/string.d:478-520, 775-831) for n pairs of host sequences.  Pair i is
+ *      ref[ref_off[i] .. ref_off[i + 1]) against qry[qry_off[i] .. qry_off[i + 1]); two bases match when their bytes are
+ *      equal.  free_shift != 0: F[i][0] = F[0][j] = 0; the score is still F[rl][ql] and the traceback still starts at
+ *      that corner and pads with deletions, then insertions, at a border.  Ties: diagonal, then insertion, then deletion.
+ *      out: a dh_edit_paths of n entries (every accessor and both formatters apply): op_off / ops as for records,
+ *      score[i] = F[rl][ql], tile_off all zero, no tile scores, general_tiles = 0.
+ *      status (n entries or NULL): DH_NW_OK, or DH_NW_BAND_EXCEEDED for a pair whose alignment cannot be proven exact
+ *      inside the widest band the kernel serves (DH_NW_MAX_BAND diagonals; a pair with rl + ql < DH_NW_MAX_BAND always
+ *      fits).  Such a pair has score -1 and no ops, the call still succeeds (the reference's AlignmentException, which a
+ *      caller catches per alignment).
+ *      DH_EINVAL, found on the host before anything is launched: offsets that do not start at >= 0 or decrease, a sequence
+ *      longer than DH_NW_MAX_LEN (which bounds the decision scratch of one pair at the widest band to 64 MiB).
+ *      A pair with an empty sequence is answered on the host. */
+#define DH_NW_OK 0
+#define DH_NW_BAND_EXCEEDED 1
+#define DH_NW_MAX_LEN 65536
+#define DH_NW_MAX_BAND 4096
+int dh_nw_batch(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off /* n + 1 */, const uint8_t *qry,
+                const int64_t *qry_off /* n + 1 */, int64_t n, int32_t free_shift, dh_edit_paths **out,
+                int32_t *status /* n entries or NULL */);
+
 /* ---- gap-closed assembly writer (host only): the linear-scaffold subset of `dentist output`
  *      (source/dentist/commands/output.d:743-925): header "<id>\tscaffold-<first contig id>", contig
  *      slices lower case, insertions upper case (highlight != 0), unclosed gaps as 'n' runs, lines

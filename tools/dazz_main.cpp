@@ -27,6 +27,9 @@
 //   LAtranspose [-b] <A:db|dam> <B:db|dam> <in:las> <out:las>   the same alignments with the roles of the sequences exchanged
 //                                    (dh_la_transpose: the file `damapper -C` names <B>.<A>.las, dazzler.d:6158-6170, as the
 //                                    exact transposition of <in>); -b sets the chain flags
+//   DBnw [-f] [-a] [-w<int(100)>] <A:db|dam> <B:db|dam> [first-last]   read i of A against read i of B end to end
+//                                    (dh_nw_batch: findAlignment, util/string.d:478-520; -f free shift): pair, lengths,
+//                                    score, matches, columns, extended cigar; -a adds the alignment text
 // DENTIST only sees exit codes, files and stdout of these tools; flags it never emits are rejected.
 #include <algorithm>
 #include <cmath>
@@ -886,6 +889,89 @@ static int tool_latranspose(const std::vector<std::string> &args)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- DBnw
+// Read i of A against read i of B, globally (dh_nw_batch; -f: free shift).  One line per pair, tab separated: pair number
+// (1-based), length of the A read, length of the B read, score, matches, alignment columns (the two numbers
+// `check-results` reads from stretcher's "# Identity:" line), extended cigar.  A pair whose band the kernel does not serve
+// prints score -1, 0 matches, 0 columns and the cigar "*".
+static int tool_dbnw(const std::vector<std::string> &args)
+{
+    bool show = false, fs = false;
+    int width = 100;
+    std::vector<std::string> pos;
+    for (const std::string &a : args) {
+        if (a == "-a")
+            show = true;
+        else if (a == "-f")
+            fs = true;
+        else if (a.compare(0, 2, "-w") == 0)
+            width = atoi(a.c_str() + 2);
+        else if (a[0] == '-')
+            die("unknown option " + a);
+        else
+            pos.push_back(a);
+    }
+    long long r0 = 1, r1 = -1;
+    if (pos.size() >= 3 && pos.back().find_first_not_of("0123456789-") == std::string::npos) {
+        if (sscanf(pos.back().c_str(), "%lld-%lld", &r0, &r1) != 2) {
+            if (sscanf(pos.back().c_str(), "%lld", &r0) != 1) die("bad pair range " + pos.back());
+            r1 = r0;
+        }
+        pos.pop_back();
+    }
+    if (pos.size() != 2 || width < 1) die("usage: DBnw [-f] [-a] [-w<int(100)>] <A:db|dam> <B:db|dam> [first-last]");
+    dh_ctx *ctx = nullptr;
+    CHK(dh_ctx_create(0, nullptr, &ctx));
+    dh_dazz *da = open_dazz(pos[0]), *dbz = open_dazz(pos[1]);
+    const int64_t n = std::min(dh_dazz_nreads(da), dh_dazz_nreads(dbz));
+    if (r1 < 0) r1 = n;
+    if (r0 < 1 || r1 > n || r0 > r1 + 1) die("pair range outside the DBs (" + std::to_string(n) + " pairs)");
+    const int64_t cnt = r1 - r0 + 1;
+    const int64_t *aoff = dh_dazz_offsets(da) + (r0 - 1), *boff = dh_dazz_offsets(dbz) + (r0 - 1);
+    dh_edit_paths *ep = nullptr;
+    std::vector<int32_t> status((size_t)cnt + 1);
+    CHK(dh_nw_batch(ctx, dh_dazz_bases(da), aoff, dh_dazz_bases(dbz), boff, cnt, fs ? 1 : 0, &ep, status.data()));
+    const int64_t *op_off = dh_edit_paths_op_off(ep);
+    const uint8_t *ops = dh_edit_paths_ops(ep);
+    const int32_t *score = dh_edit_paths_score(ep);
+    std::vector<char> text;
+    for (int64_t i = 0; i < cnt; i++) {
+        const uint8_t *o = ops + op_off[i];
+        const int64_t no = op_off[i + 1] - op_off[i];
+        const long long alen = aoff[i + 1] - aoff[i], blen = boff[i + 1] - boff[i];
+        if (status[(size_t)i] != DH_NW_OK) {
+            printf("%lld\t%lld\t%lld\t-1\t0\t0\t*\n", (long long)(r0 + i), alen, blen);
+            continue;
+        }
+        int64_t nmatch = 0;
+        for (int64_t k = 0; k < no; k++) nmatch += o[k] == 0;
+        const int64_t clen = dh_format_cigar(o, no, 1, nullptr, 0);
+        if (clen < 0) die(dh_last_error());
+        text.resize((size_t)clen + 1);
+        text[0] = 0;
+        dh_format_cigar(o, no, 1, text.data(), clen + 1);
+        printf("%lld\t%lld\t%lld\t%d\t%lld\t%lld\t%s\n", (long long)(r0 + i), alen, blen, score[i], (long long)nmatch, (long long)no,
+               text.data());
+        if (!show) continue;
+        const int64_t tl = dh_format_alignment(dh_dazz_bases(da) + aoff[i], dh_dazz_bases(dbz) + boff[i], o, no, width, nullptr, 0);
+        if (tl < 0) die(dh_last_error());
+        text.resize((size_t)tl + 1);
+        text[0] = 0;
+        dh_format_alignment(dh_dazz_bases(da) + aoff[i], dh_dazz_bases(dbz) + boff[i], o, no, width, text.data(), tl + 1);
+        putchar('#');
+        for (int64_t k = 0; k < tl; k++) {
+            putchar(text[(size_t)k]);
+            if (text[(size_t)k] == '\n') putchar('#');
+        }
+        putchar('\n');
+    }
+    dh_edit_paths_destroy(ep);
+    dh_dazz_close(dbz);
+    dh_dazz_close(da);
+    dh_ctx_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     g_tool = argv[0];
@@ -915,6 +1001,7 @@ int main(int argc, char **argv)
     if (g_tool == "TANmask") return tool_tanmask(args);
     if (g_tool == "LApaf") return tool_lapaf(args);
     if (g_tool == "LAtranspose") return tool_latranspose(args);
+    if (g_tool == "DBnw") return tool_dbnw(args);
     die("unknown tool (expected fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv "
         "computeintrinsicqv daccord merge-insertions)");
     return 1;
