@@ -6,7 +6,7 @@ CSRC := dentist_amd/csrc
 LIB := dentist_amd/libdentist_hip.so
 SIM := dentist_amd/sim/libdh_sim.so
 
-DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw
+DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher
 TOOLS := tools/daligner tools/damapper tools/datander tools/dazz_tools $(addprefix tools/,$(DAZZ_TOOLS))
 
 all: $(LIB) $(SIM) oracle $(TOOLS)
@@ -72,4 +72,8 @@ tests/native/libdh_transpose_host.so: tests/native/transpose_host.cpp dentist_am
 
 # the lane code of the global-alignment kernel (dentist_amd/csrc/dh_nw.h) compiled for the CPU: test infrastructure
 tests/native/libdh_nw_host.so: tests/native/nw_host.cpp dentist_amd/csrc/dh_nw.h dentist_amd/csrc/dh_editpath.h dentist_amd/csrc/dh_bitvec.h
+	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -Wno-unknown-pragmas -o $@ $<
+
+# the lane code of the affine-gap global-alignment kernel (dentist_amd/csrc/dh_nwa.h) compiled for the CPU: test infrastructure
+tests/native/libdh_nwa_host.so: tests/native/nwa_host.cpp dentist_amd/csrc/dh_nwa.h dentist_amd/csrc/dh_nw.h dentist_amd/csrc/dh_editpath.h dentist_amd/csrc/dh_bitvec.h
 	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -Wno-unknown-pragmas -o $@ $<

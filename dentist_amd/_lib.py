@@ -98,7 +98,7 @@ SYMBOLS = [
     "dh_la_edit_paths", "dh_la_set_edit_paths", "dh_edit_paths_destroy", "dh_edit_paths_count", "dh_edit_paths_op_off",
     "dh_edit_paths_ops", "dh_edit_paths_score", "dh_edit_paths_tile_off", "dh_edit_paths_tile_score",
     "dh_edit_paths_general_tiles", "dh_format_cigar", "dh_format_alignment", "dh_la_transpose", "dh_la_set_transpose",
-    "dh_nw_batch",
+    "dh_nw_batch", "dh_nw_affine_batch", "dh_format_pair",
 ]
 
 _LIB = None
@@ -226,6 +226,9 @@ def lib():
     L.dh_format_alignment.argtypes = [vp, vp, vp, i64, i32, vp, i64]
     L.dh_format_alignment.restype = i64
     L.dh_nw_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, ctypes.POINTER(vp), vp]
+    L.dh_nw_affine_batch.argtypes = [vp, vp, vp, vp, vp, i64, vp, ctypes.POINTER(vp), vp]
+    L.dh_format_pair.argtypes = [ctypes.c_char_p, vp, i64, ctypes.c_char_p, vp, i64, vp, i64, i32, vp, i64, vp, i64]
+    L.dh_format_pair.restype = i64
     _LIB = L
     return L
 
@@ -418,6 +421,32 @@ class Context:
                                  ctypes.byref(h), status.ctypes.data))
         return EditPaths(h), status
 
+    def nw_affine_batch(self, refs, qrys, scoring=None):
+        """dh_nw_affine_batch: the global alignment of refs[i] against qrys[i] with affine gap costs (what EMBOSS stretcher
+        computes).  scoring: (match, mismatch, gap_open, gap_extend), None = (5, -4, 16, 4); a gap of k bases scores
+        -(gap_open + k * gap_extend).  Returns (EditPaths, status) as nw_batch does; score[i] is the alignment score."""
+        if len(refs) != len(qrys):
+            raise ValueError("refs and qrys differ in length")
+        r, roff = _concat_seqs(refs)
+        q, qoff = _concat_seqs(qrys)
+        return self.nw_affine_batch_raw(r, roff, q, qoff, scoring)
+
+    def nw_affine_batch_raw(self, ref, ref_off, qry, qry_off, scoring=None):
+        """nw_affine_batch on concatenated sequences, laid out as for nw_batch_raw."""
+        r, q = np.ascontiguousarray(ref, dtype=np.uint8), np.ascontiguousarray(qry, dtype=np.uint8)
+        roff, qoff = np.ascontiguousarray(ref_off, dtype=np.int64), np.ascontiguousarray(qry_off, dtype=np.int64)
+        if len(roff) != len(qoff) or len(roff) < 1:
+            raise ValueError("ref_off and qry_off need n + 1 entries each")
+        n = len(roff) - 1
+        if n and (int(roff.max()) > len(r) or int(qoff.max()) > len(q)):
+            raise ValueError("an offset lies behind the end of the sequences")
+        sc = _scoring(scoring)
+        status = np.zeros(n, dtype=np.int32)
+        h = ctypes.c_void_p()
+        _check(lib().dh_nw_affine_batch(self._h, r.ctypes.data, roff.ctypes.data, q.ctypes.data, qoff.ctypes.data, n,
+                                        sc.ctypes.data if sc is not None else None, ctypes.byref(h), status.ctypes.data))
+        return EditPaths(h), status
+
     def transpose(self, A, B, las, trace=None, tspace=None, select_best=False):
         """dh_la_transpose: the same alignments with the roles of the sequences exchanged (aread = B read, trace points on
         the B read's grid), from their edit paths.  Returns (las', trace', src_index), LAsort order; src_index[i] is the
@@ -503,6 +532,34 @@ NW_OK, NW_BAND_EXCEEDED = 0, 1
 NW_MAX_LEN, NW_MAX_BAND = 65536, 4096
 
 
+# limits the kernels' instantiations decide: read from include/dentist_hip.h, not repeated here -- on first use, so that
+# importing the package needs nothing outside it
+_HEADER_LIMITS = {"NWA_MAX_LEN": "DH_NWA_MAX_LEN", "NWA_MAX_BAND": "DH_NWA_MAX_BAND"}
+
+
+def __getattr__(name):
+    if name not in _HEADER_LIMITS:
+        raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+    import re
+    with open(os.path.join(_HERE, "..", "include", "dentist_hip.h")) as f:
+        m = re.search(r"^#define\s+" + _HEADER_LIMITS[name] + r"\s+(\d+)\s*$", f.read(), flags=re.M)
+    if not m:
+        raise RuntimeError(f"{_HEADER_LIMITS[name]} is not defined in include/dentist_hip.h")
+    globals()[name] = int(m.group(1))
+    return globals()[name]
+NWA_DEFAULT_SCORING = (5, -4, 16, 4)
+
+
+def _scoring(scoring):
+    """dh_nw_scoring as four int32, None for the library's default"""
+    if scoring is None:
+        return None
+    sc = np.asarray(scoring, dtype=np.int64)
+    if sc.shape != (4,) or np.any(np.abs(sc) > 2 ** 31 - 1):
+        raise ValueError("scoring is (match, mismatch, gap_open, gap_extend), four 32-bit integers")
+    return np.ascontiguousarray(sc, dtype=np.int32)
+
+
 def _concat_seqs(seqs):
     arrs = [_seq_bytes(x) for x in seqs]
     off = np.zeros(len(arrs) + 1, dtype=np.int64)
@@ -523,6 +580,16 @@ def format_alignment(a, b, ops, width=0):
     if int(np.count_nonzero(o != 2)) > len(sa) or int(np.count_nonzero(o != 1)) > len(sb):
         raise ValueError("the ops consume more bases than the sequences have")
     return _format(lib().dh_format_alignment, sa.ctypes.data, sb.ctypes.data, o.ctypes.data, len(o), int(width))
+
+
+def format_pair(name_a, a, name_b, b, ops, score, scoring=None, width=0):
+    """dh_format_pair: the alignment as EMBOSS `pair` text (what `dentist check-results` reads from stretcher); width 0
+    writes one block."""
+    o = np.ascontiguousarray(ops, dtype=np.uint8)
+    sa, sb = _seq_bytes(a), _seq_bytes(b)
+    sc = _scoring(scoring)
+    return _format(lib().dh_format_pair, name_a.encode(), sa.ctypes.data, len(sa), name_b.encode(), sb.ctypes.data, len(sb),
+                   o.ctypes.data, len(o), int(score), sc.ctypes.data if sc is not None else None, int(width))
 
 
 class DeviceTrace:

@@ -110,6 +110,8 @@ enum DhSlot : int {
     // global alignment (run_launch, dh_nw.cpp): live for one launch group of pairs; SLOT_NW_REF / SLOT_NW_QRY hold the
     // sequences of a chunk for all its launches
     SLOT_NW_REF, SLOT_NW_QRY, SLOT_NW_PAIRS, SLOT_NW_DM, SLOT_NW_OW, SLOT_NW_RES, SLOT_NW_COPY, SLOT_NW_OPS,
+    // affine-gap global alignment (run_launch, dh_nwa.cpp): the same lifetimes
+    SLOT_NWA_REF, SLOT_NWA_QRY, SLOT_NWA_PAIRS, SLOT_NWA_DM, SLOT_NWA_OW, SLOT_NWA_RES, SLOT_NWA_COPY, SLOT_NWA_OPS,
     DH_SLOT_COUNT
 };
 // The words of SLOT_STATUS (DH_STW_COUNT x int32), one buffer with three users.  All of them run on the context's stream:

@@ -115,15 +115,15 @@ EP_HD int32_t band_width(int32_t rl, int32_t ql, int64_t w, int32_t free_shift)
 }
 
 // the half-width of the attempt after one at w_prev (0: the first, at w0): twice as much, or the largest whose band the
-// widest kernel still serves; -1 when that is no wider than w_prev
-inline int64_t next_w(int32_t rl, int32_t ql, int32_t free_shift, int64_t w_prev, int64_t w0)
+// widest kernel (max_w columns) still serves; -1 when that is no wider than w_prev
+inline int64_t next_w(int32_t rl, int32_t ql, int32_t free_shift, int64_t w_prev, int64_t w0, int32_t max_w = NW_MAX_W)
 {
     const int64_t w = w_prev ? 2 * w_prev : w0;
-    if (band_width(rl, ql, w, free_shift) <= NW_MAX_W) return w;
+    if (band_width(rl, ql, w, free_shift) <= max_w) return w;
     int64_t a = w_prev, b = w;  // the band of b does not fit
     while (b - a > 1) {
         const int64_t m = (a + b) / 2;
-        if (band_width(rl, ql, m, free_shift) <= NW_MAX_W)
+        if (band_width(rl, ql, m, free_shift) <= max_w)
             a = m;
         else
             b = m;
@@ -284,5 +284,26 @@ EP_HD EpResult traceback(int32_t rl, int32_t ql, int32_t lo, int32_t W, int32_t 
 }
 
 }  // namespace nw
+
+#if defined(__HIPCC__)
+// inclusive prefix minimum over the 64 lanes: row_shr 1, 2, 4, 8 inside the rows of 16, then row_bcast:15 / row_bcast:31
+// (the sequence of ep_scan_add); a lane without a source keeps its own value.  Shared by k_nw and k_nwa.
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ int32_t nw_dpp_min(int32_t v)
+{
+    const int32_t o = __builtin_amdgcn_update_dpp(v, v, CTRL, ROWMASK, 0xF, false);
+    return v < o ? v : o;
+}
+__device__ __forceinline__ int32_t nw_scan_min(int32_t v)
+{
+    v = nw_dpp_min<0x111, 0xF>(v);
+    v = nw_dpp_min<0x112, 0xF>(v);
+    v = nw_dpp_min<0x114, 0xF>(v);
+    v = nw_dpp_min<0x118, 0xF>(v);
+    v = nw_dpp_min<0x142, 0xA>(v);
+    v = nw_dpp_min<0x143, 0xC>(v);
+    return v;
+}
+#endif
 
 #endif

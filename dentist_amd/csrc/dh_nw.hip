@@ -10,26 +10,7 @@
 // pair at 129 diagonals is 200 KB.  The host bounds the footprint by the pairs it hands to a launch (DH_NW_CHUNK_KB).
 #include <hip/hip_runtime.h>
 
-#include "dh_nw.h"
-
-// inclusive prefix minimum over the 64 lanes: row_shr 1, 2, 4, 8 inside the rows of 16, then row_bcast:15 / row_bcast:31
-// (the sequence of ep_scan_add); a lane without a source keeps its own value
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ int32_t nw_dpp_min(int32_t v)
-{
-    const int32_t o = __builtin_amdgcn_update_dpp(v, v, CTRL, ROWMASK, 0xF, false);
-    return v < o ? v : o;
-}
-__device__ __forceinline__ int32_t nw_scan_min(int32_t v)
-{
-    v = nw_dpp_min<0x111, 0xF>(v);
-    v = nw_dpp_min<0x112, 0xF>(v);
-    v = nw_dpp_min<0x114, 0xF>(v);
-    v = nw_dpp_min<0x118, 0xF>(v);
-    v = nw_dpp_min<0x142, 0xA>(v);
-    v = nw_dpp_min<0x143, 0xC>(v);
-    return v;
-}
+#include "dh_nw.h"  // nw_scan_min: the DPP prefix minimum
 
 template <int CPL, int NS>
 __global__ void __launch_bounds__(64)

@@ -753,6 +753,41 @@ int dh_nw_batch(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off /* n + 1
                 const int64_t *qry_off /* n + 1 */, int64_t n, int32_t free_shift, dh_edit_paths **out,
                 int32_t *status /* n entries or NULL */);
 
+/* ---- global alignment with affine gap costs (Gotoh): what EMBOSS `stretcher` computes for `dentist check-results`
+ *      (commands/checkResults.d:1270-1291, 2059-2162), for n pairs of host sequences laid out as for dh_nw_batch.
+ *      Scoring: two equal bytes score match, any other pair mismatch; a gap of k bases scores -(gap_open + k gap_extend),
+ *      end gaps included.  sc == NULL: {5, -4, 16, 4}, the values EMBOSS documents for nucleotide stretcher (EDNAFULL,
+ *      gapopen 16, gapextend 4).  UNPINNED: whether EMBOSS charges open + k ext or open + (k - 1) ext for a gap, and which
+ *      of several optimal alignments it reports, could not be checked against its source; the other convention is
+ *      {match, mismatch, gap_open - gap_extend, gap_extend}.
+ *      Ties: among the sources that attain a cell's value the diagonal, then the insertion, then the deletion, except
+ *      that the diagonal yields a tie to a gap state unless its step costs at least a gap base (an equal pair always
+ *      yields; an unequal one keeps the tie only if 2 (match - mismatch) >= 2 gap_extend + match, as 18 >= 13 under the
+ *      default scoring); inside a gap, closing it wins over extending it.  This is findAlignment's
+ *      walk, which moves to the neighbour of the smallest score: with {0, -1, 0, 1} ops and -score are dh_nw_batch's
+ *      (free_shift = 0).
+ *      out: a dh_edit_paths as dh_nw_batch returns it, score[i] = the alignment score (maximised, signed).
+ *      status: DH_NW_OK, or DH_NW_BAND_EXCEEDED (score -1, no ops, the call still succeeds) for a pair whose alignment cannot
+ *      be proven exact inside DH_NWA_MAX_BAND diagonals.
+ *      DH_EINVAL, found on the host before anything is launched: what dh_nw_batch refuses (with DH_NWA_MAX_LEN), match <
+ *      mismatch, 2 gap_extend + match <= 0, gap_open < 0, and values so large that the cost of two sequences of
+ *      DH_NWA_MAX_LEN could overflow.  A pair with an empty sequence is answered on the host: one gap.
+ *      dh_format_pair (host only) writes the alignment as EMBOSS `pair` text: comment lines (among them "# Identity:
+ *      n/m (p%)"), then per block of `width` columns (0: one block) "%-13.13s %6d <bases> %6d" for a, 21 blanks and the
+ *      markup ('|' equal, '.' unequal, ' ' gap, as long as the block), the same for b.  Bases print as ACGTN (codes 0..4 or
+ *      letters; anything else N), gaps as '-'.  The sizing convention is dh_format_alignment's. */
+typedef struct {
+    int32_t match, mismatch, gap_open, gap_extend;
+} dh_nw_scoring;
+#define DH_NWA_MAX_LEN 65536
+#define DH_NWA_MAX_BAND 2048
+int dh_nw_affine_batch(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off /* n + 1 */, const uint8_t *qry,
+                       const int64_t *qry_off /* n + 1 */, int64_t n, const dh_nw_scoring *sc /* NULL: 5,-4,16,4 */,
+                       dh_edit_paths **out, int32_t *status /* n entries or NULL */);
+int64_t dh_format_pair(const char *name_a, const uint8_t *a, int64_t la, const char *name_b, const uint8_t *b, int64_t lb,
+                       const uint8_t *ops, int64_t nops, int32_t score, const dh_nw_scoring *sc /* NULL: the default */,
+                       int64_t width, char *out, int64_t cap);
+
 /* ---- gap-closed assembly writer (host only): the linear-scaffold subset of `dentist output`
  *      (source/dentist/commands/output.d:743-925): header "<id>\tscaffold-<first contig id>", contig
  *      slices lower case, insertions upper case (highlight != 0), unclosed gaps as 'n' runs, lines

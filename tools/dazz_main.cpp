@@ -30,6 +30,10 @@
 //   DBnw [-f] [-a] [-w<int(100)>] <A:db|dam> <B:db|dam> [first-last]   read i of A against read i of B end to end
 //                                    (dh_nw_batch: findAlignment, util/string.d:478-520; -f free shift): pair, lengths,
 //                                    score, matches, columns, extended cigar; -a adds the alignment text
+//   stretcher [--auto] [--stdout | --outfile=<file>] [--aformat=pair] [--awidth=<int(50)>] [--sreverse2] [--gapopen=<int(16)>]
+//             [--gapextend=<int(4)>] <a:fasta> <b:fasta>   (one dash or two) the first record of each file aligned end to end
+//                                    with affine gap costs (dh_nw_affine_batch), written as EMBOSS `pair` text
+//                                    (dh_format_pair): the call of `dentist check-results` (commands/checkResults.d:2091-2100)
 // DENTIST only sees exit codes, files and stdout of these tools; flags it never emits are rejected.
 #include <algorithm>
 #include <cmath>
@@ -972,6 +976,109 @@ static int tool_dbnw(const std::vector<std::string> &args)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- stretcher
+// The first record of a FASTA file: its name (the header's first word) and its bases as codes 0..4 (letters outside ACGT
+// become N).
+static void first_fasta_record(const std::string &path, std::string &name, std::vector<uint8_t> &seq)
+{
+    FILE *f = fopen(path.c_str(), "r");
+    if (!f) die("cannot open " + path);
+    const std::string text = slurp(f);
+    fclose(f);
+    size_t p = text.find('>');
+    if (p == std::string::npos || (p > 0 && text[p - 1] != '\n')) die("no FASTA record in " + path);
+    size_t eol = text.find('\n', p);
+    if (eol == std::string::npos) eol = text.size();
+    const std::string header = text.substr(p + 1, eol - p - 1);
+    name = header.substr(0, header.find_first_of(" \t\r"));
+    for (size_t k = eol; k < text.size(); k++) {
+        const char c = text[k];
+        if (c == '>' && text[k - 1] == '\n') break;
+        if (c == '\n' || c == '\r' || c == ' ' || c == '\t') continue;
+        switch (c | 32) {
+            case 'a': seq.push_back(0); break;
+            case 'c': seq.push_back(1); break;
+            case 'g': seq.push_back(2); break;
+            case 't': seq.push_back(3); break;
+            default: seq.push_back(4);
+        }
+    }
+}
+
+static int tool_stretcher(const std::vector<std::string> &args)
+{
+    const char *usage = "usage: stretcher [--auto] [--stdout | --outfile=<file>] [--aformat=pair] [--awidth=<int(50)>] [--sreverse2] "
+                        "[--gapopen=<int(16)>] [--gapextend=<int(4)>] <a:fasta> <b:fasta>";
+    dh_nw_scoring sc = {5, -4, 16, 4};
+    long long width = 50;
+    bool rev2 = false;
+    std::string outfile;
+    std::vector<std::string> pos;
+    for (const std::string &a : args) {
+        if (a.size() < 2 || a[0] != '-') {
+            pos.push_back(a);
+            continue;
+        }
+        const std::string opt = a.substr(a[1] == '-' ? 2 : 1);
+        const size_t eq = opt.find('=');
+        const std::string key = opt.substr(0, eq), val = eq == std::string::npos ? "" : opt.substr(eq + 1);
+        char *end = nullptr;
+        const long long num = strtoll(val.c_str(), &end, 10);
+        const bool is_num = !val.empty() && *end == 0;
+        if ((key == "auto" || key == "stdout") && eq == std::string::npos)
+            ;
+        else if (key == "sreverse2" && eq == std::string::npos)
+            rev2 = true;
+        else if (key == "aformat") {
+            if (val != "pair") die("--aformat=" + val + ": only the pair format is written");
+        } else if (key == "awidth" && is_num && num >= 1)
+            width = num;
+        else if (key == "gapopen" && is_num && num >= 0 && num <= INT32_MAX)
+            sc.gap_open = (int32_t)num;
+        else if (key == "gapextend" && is_num && num >= 0 && num <= INT32_MAX)
+            sc.gap_extend = (int32_t)num;
+        else if (key == "outfile" && !val.empty())
+            outfile = val;
+        else
+            die("unknown or malformed option " + a + "\n" + usage);
+    }
+    if (pos.size() != 2) die(usage);
+    std::string name[2];
+    std::vector<uint8_t> seq[2];
+    for (int k = 0; k < 2; k++) first_fasta_record(pos[(size_t)k], name[k], seq[k]);
+    if (rev2) {
+        std::reverse(seq[1].begin(), seq[1].end());
+        for (uint8_t &c : seq[1]) c = c < 4 ? (uint8_t)(3 - c) : c;
+    }
+    dh_ctx *ctx = nullptr;
+    CHK(dh_ctx_create(0, nullptr, &ctx));
+    const int64_t aoff[2] = {0, (int64_t)seq[0].size()}, boff[2] = {0, (int64_t)seq[1].size()};
+    dh_edit_paths *ep = nullptr;
+    int32_t status = 0;
+    CHK(dh_nw_affine_batch(ctx, seq[0].data(), aoff, seq[1].data(), boff, 1, &sc, &ep, &status));
+    if (status != DH_NW_OK)
+        die("the alignment of " + name[0] + " (" + std::to_string(seq[0].size()) + " bases) and " + name[1] + " (" +
+                std::to_string(seq[1].size()) + " bases) cannot be proven optimal inside " + std::to_string(DH_NWA_MAX_BAND) +
+                " diagonals, the widest band the kernel serves; nothing was written",
+            2);
+    const uint8_t *ops = dh_edit_paths_ops(ep);
+    const int64_t nops = dh_edit_paths_op_off(ep)[1];
+    const int32_t score = dh_edit_paths_score(ep)[0];
+    const int64_t tl = dh_format_pair(name[0].c_str(), seq[0].data(), aoff[1], name[1].c_str(), seq[1].data(), boff[1], ops, nops, score,
+                                      &sc, width, nullptr, 0);
+    if (tl < 0) die(dh_last_error());
+    std::vector<char> text((size_t)tl + 1);
+    dh_format_pair(name[0].c_str(), seq[0].data(), aoff[1], name[1].c_str(), seq[1].data(), boff[1], ops, nops, score, &sc, width,
+                   text.data(), tl + 1);
+    FILE *o = outfile.empty() ? stdout : fopen(outfile.c_str(), "w");
+    if (!o) die("cannot write " + outfile);
+    const bool ok = fwrite(text.data(), 1, (size_t)tl, o) == (size_t)tl;
+    if ((o != stdout ? fclose(o) : fflush(o)) != 0 || !ok) die("write error");
+    dh_edit_paths_destroy(ep);
+    dh_ctx_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     g_tool = argv[0];
@@ -1002,6 +1109,7 @@ int main(int argc, char **argv)
     if (g_tool == "LApaf") return tool_lapaf(args);
     if (g_tool == "LAtranspose") return tool_latranspose(args);
     if (g_tool == "DBnw") return tool_dbnw(args);
+    if (g_tool == "stretcher") return tool_stretcher(args);
     die("unknown tool (expected fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv "
         "computeintrinsicqv daccord merge-insertions)");
     return 1;
