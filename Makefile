@@ -6,7 +6,7 @@ CSRC := dentist_amd/csrc
 LIB := dentist_amd/libdentist_hip.so
 SIM := dentist_amd/sim/libdh_sim.so
 
-DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher
+DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index
 TOOLS := tools/daligner tools/damapper tools/datander tools/dazz_tools $(addprefix tools/,$(DAZZ_TOOLS))
 
 all: $(LIB) $(SIM) oracle $(TOOLS)
@@ -77,3 +77,12 @@ tests/native/libdh_nw_host.so: tests/native/nw_host.cpp dentist_amd/csrc/dh_nw.h
 # the lane code of the affine-gap global-alignment kernel (dentist_amd/csrc/dh_nwa.h) compiled for the CPU: test infrastructure
 tests/native/libdh_nwa_host.so: tests/native/nwa_host.cpp dentist_amd/csrc/dh_nwa.h dentist_amd/csrc/dh_nw.h dentist_amd/csrc/dh_editpath.h dentist_amd/csrc/dh_bitvec.h
 	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -Wno-unknown-pragmas -o $@ $<
+
+# the lane code and the host planning of the exact-match locator (dentist_amd/csrc/dh_locate.h) compiled for the CPU: test infrastructure
+tests/native/liblocate_host.so: tests/native/locate_host.cpp dentist_amd/csrc/dh_locate.h
+	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -Wno-unknown-pragmas -o $@ $<
+
+# the same harness and a stand-alone main under the host sanitizers (a program of its own: nothing is preloaded); run it once
+# after a change to dh_locate.h -- the two-word loads at the end of the packed text are where this code would overrun
+tests/native/locate_host_san: tests/native/locate_host_main.cpp tests/native/locate_host.cpp dentist_amd/csrc/dh_locate.h
+	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -Wno-unknown-pragmas -o $@ tests/native/locate_host_main.cpp tests/native/locate_host.cpp

@@ -58,6 +58,10 @@ INSERTION_DTYPE = np.dtype([(n, "<i4") for n in (
     "right_abpos", "ins_begin", "ins_end", "comp", "cons_len", "left_diffs", "right_diffs", "join")]
     + [("cons_off", "<i8"), ("contig_right", "<i4"), ("pad", "<i4")])
 
+# dh_exact_hit (32 bytes): one exact occurrence of a query (complement 1: of its reverse complement) in a reference record
+EXACT_HIT_DTYPE = np.dtype([("query", "<i4"), ("ref", "<i4"), ("begin", "<i8"), ("end", "<i8"), ("complement", "<i4"),
+                            ("pad", "<i4")])
+
 LA_DTYPE = np.dtype([("tlen", "<i4"), ("diffs", "<i4"), ("abpos", "<i4"), ("bbpos", "<i4"),
                      ("aepos", "<i4"), ("bepos", "<i4"), ("flags", "<u4"), ("aread", "<i4"),
                      ("bread", "<i4"), ("pad", "<i4"), ("toff", "<i8")])
@@ -99,6 +103,7 @@ SYMBOLS = [
     "dh_edit_paths_ops", "dh_edit_paths_score", "dh_edit_paths_tile_off", "dh_edit_paths_tile_score",
     "dh_edit_paths_general_tiles", "dh_format_cigar", "dh_format_alignment", "dh_la_transpose", "dh_la_set_transpose",
     "dh_nw_batch", "dh_nw_affine_batch", "dh_format_pair",
+    "dh_exact_locate", "dh_exact_hits_destroy", "dh_exact_hits_count", "dh_exact_hits_records",
 ]
 
 _LIB = None
@@ -229,6 +234,13 @@ def lib():
     L.dh_nw_affine_batch.argtypes = [vp, vp, vp, vp, vp, i64, vp, ctypes.POINTER(vp), vp]
     L.dh_format_pair.argtypes = [ctypes.c_char_p, vp, i64, ctypes.c_char_p, vp, i64, vp, i64, i32, vp, i64, vp, i64]
     L.dh_format_pair.restype = i64
+    L.dh_exact_locate.argtypes = [vp, vp, vp, i64, vp, vp, i64, i32, ctypes.POINTER(vp)]
+    L.dh_exact_hits_destroy.argtypes = [vp]
+    L.dh_exact_hits_destroy.restype = None
+    L.dh_exact_hits_count.argtypes = [vp]
+    L.dh_exact_hits_count.restype = i64
+    L.dh_exact_hits_records.argtypes = [vp]
+    L.dh_exact_hits_records.restype = vp
     _LIB = L
     return L
 
@@ -446,6 +458,35 @@ class Context:
         _check(lib().dh_nw_affine_batch(self._h, r.ctypes.data, roff.ctypes.data, q.ctypes.data, qoff.ctypes.data, n,
                                         sc.ctypes.data if sc is not None else None, ctypes.byref(h), status.ctypes.data))
         return EditPaths(h), status
+
+    def exact_locate(self, refs, queries, both_strands=True):
+        """dh_exact_locate: every exact occurrence of queries[j] (and, with both_strands, of its reverse complement) in the
+        records refs[i]; sequences are base-code arrays (0..3).  Returns a structured array of EXACT_HIT_DTYPE ordered by
+        query, then strand (forward first), then (ref, begin); begin / end are 0-based, right-open, relative to the record."""
+        r, roff = _concat_seqs(refs)
+        q, qoff = _concat_seqs(queries)
+        return self.exact_locate_raw(r, roff, q, qoff, both_strands)
+
+    def exact_locate_raw(self, ref, ref_off, qry, qry_off, both_strands=True):
+        """exact_locate on concatenated sequences: record i is ref[ref_off[i]:ref_off[i + 1]], query j likewise."""
+        r, q = np.ascontiguousarray(ref, dtype=np.uint8), np.ascontiguousarray(qry, dtype=np.uint8)
+        roff, qoff = np.ascontiguousarray(ref_off, dtype=np.int64), np.ascontiguousarray(qry_off, dtype=np.int64)
+        if len(roff) < 1 or len(qoff) < 1:
+            raise ValueError("ref_off and qry_off need n + 1 entries each")
+        if (len(roff) > 1 and int(roff.max()) > len(r)) or (len(qoff) > 1 and int(qoff.max()) > len(q)):
+            raise ValueError("an offset lies behind the end of the sequences")
+        h = ctypes.c_void_p()
+        L = lib()
+        _check(L.dh_exact_locate(self._h, r.ctypes.data, roff.ctypes.data, len(roff) - 1, q.ctypes.data, qoff.ctypes.data,
+                                 len(qoff) - 1, int(bool(both_strands)), ctypes.byref(h)))
+        try:
+            n = L.dh_exact_hits_count(h)
+            out = np.zeros(n, dtype=EXACT_HIT_DTYPE)
+            if n:
+                ctypes.memmove(out.ctypes.data, L.dh_exact_hits_records(h), n * EXACT_HIT_DTYPE.itemsize)
+        finally:
+            L.dh_exact_hits_destroy(h)
+        return out
 
     def transpose(self, A, B, las, trace=None, tspace=None, select_best=False):
         """dh_la_transpose: the same alignments with the roles of the sequences exchanged (aread = B read, trace points on

@@ -112,6 +112,11 @@ enum DhSlot : int {
     SLOT_NW_REF, SLOT_NW_QRY, SLOT_NW_PAIRS, SLOT_NW_DM, SLOT_NW_OW, SLOT_NW_RES, SLOT_NW_COPY, SLOT_NW_OPS,
     // affine-gap global alignment (run_launch, dh_nwa.cpp): the same lifetimes
     SLOT_NWA_REF, SLOT_NWA_QRY, SLOT_NWA_PAIRS, SLOT_NWA_DM, SLOT_NWA_OW, SLOT_NWA_RES, SLOT_NWA_COPY, SLOT_NWA_OPS,
+    // exact-match locator (dh_exact_locate, dh_locate.cpp): the packed text, the record starts and the plan of the queries
+    // live for one call; SLOT_LOC_CANDS / SLOT_LOC_COUNTER are rewritten by every scanned range, SLOT_LOC_UNITS by every
+    // batch of verify units
+    SLOT_LOC_TEXT, SLOT_LOC_STARTS, SLOT_LOC_PW, SLOT_LOC_PATS, SLOT_LOC_MEMB, SLOT_LOC_TABLE, SLOT_LOC_BITMAP, SLOT_LOC_SHORTS,
+    SLOT_LOC_CANDS, SLOT_LOC_COUNTER, SLOT_LOC_UNITS,
     DH_SLOT_COUNT
 };
 // The words of SLOT_STATUS (DH_STW_COUNT x int32), one buffer with three users.  All of them run on the context's stream:

@@ -788,6 +788,34 @@ int64_t dh_format_pair(const char *name_a, const uint8_t *a, int64_t la, const c
                        const uint8_t *ops, int64_t nops, int32_t score, const dh_nw_scoring *sc /* NULL: the default */,
                        int64_t width, char *out, int64_t cap);
 
+/* ---- exact-match locator: every exact occurrence of every query, and of its reverse complement, in a reference of nref
+ *      records -- what the reference's own external/fm-index.cpp answers when `dentist check-results` places the cropped
+ *      contigs of the true assembly in the result (commands/checkResults.d:511-565); tools/fm-index is the drop-in.  No
+ *      index is built: the reference is packed 2 bits per base, streamed once against a hash table of the queries' first
+ *      32 bases, and the candidates are compared word by word.
+ *      ref / qry: codes 0..3 (a, c, g, t), one per byte; record i is ref[ref_off[i], ref_off[i + 1]), query j likewise.
+ *      The reverse complement of a query is its codes reversed, each replaced by 3 - code.
+ *      A hit never spans two records.  Overlapping occurrences are all reported.  An empty query has no hits.
+ *      Order of the hits: by query; within a query the forward occurrences (complement 0) first, then, if both_strands,
+ *      those of the reverse complement (complement 1) -- a query equal to its own reverse complement is reported twice --
+ *      each ascending by (record, begin).  The result is the same from run to run.
+ *      begin / end: 0-based, right-open, relative to the record; for complement 1 they are where the reverse complement
+ *      lies on the forward reference.
+ *      Answered on the host without a launch: nref == 0, nqry == 0, queries longer than the longest record.
+ *      DH_EINVAL, found on the host before anything is launched: offsets that start below 0 or decrease, a code above 3,
+ *      more than 2^31 - 1 records or queries.  A reference that does not fit the device is an error, never a fallback.
+ *      Queries of 1..31 bases cost (reference bases x short queries) compares; contigs are never that short.
+ *      Development knobs (tests): DH_LOCATE_SEG (bases per verify unit, default 1 Mi), DH_LOCATE_CAND_CAP (entries of the
+ *      candidate buffer, default 1 Mi; an overflowing range is scanned again in halves, nothing is dropped). */
+typedef struct { int32_t query, ref; int64_t begin, end; int32_t complement, pad_; } dh_exact_hit;  /* 32 bytes */
+typedef struct dh_exact_hits dh_exact_hits;
+int dh_exact_locate(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off /* nref + 1 */, int64_t nref,
+                    const uint8_t *qry, const int64_t *qry_off /* nqry + 1 */, int64_t nqry,
+                    int32_t both_strands, dh_exact_hits **out);
+void dh_exact_hits_destroy(dh_exact_hits *h);
+int64_t dh_exact_hits_count(const dh_exact_hits *h);
+const dh_exact_hit *dh_exact_hits_records(const dh_exact_hits *h);
+
 /* ---- gap-closed assembly writer (host only): the linear-scaffold subset of `dentist output`
  *      (source/dentist/commands/output.d:743-925): header "<id>\tscaffold-<first contig id>", contig
  *      slices lower case, insertions upper case (highlight != 0), unclosed gaps as 'n' runs, lines

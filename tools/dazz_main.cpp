@@ -34,6 +34,10 @@
 //             [--gapextend=<int(4)>] <a:fasta> <b:fasta>   (one dash or two) the first record of each file aligned end to end
 //                                    with affine gap costs (dh_nw_affine_batch), written as EMBOSS `pair` text
 //                                    (dh_format_pair): the call of `dentist check-results` (commands/checkResults.d:2091-2100)
+//   fm-index [-P<dir>] [-r] <reference> [<queries>...]   every exact occurrence of every query line (-r: and of its reverse
+//                                    complement) in the records (lines) of <reference>, one TAB-separated line per hit
+//                                    (dh_exact_locate): the reference's external/fm-index.cpp as `dentist check-results`
+//                                    calls it (commands/checkResults.d:511-565, 654-687); leaves <reference>.fm9
 // DENTIST only sees exit codes, files and stdout of these tools; flags it never emits are rejected.
 #include <algorithm>
 #include <cmath>
@@ -42,6 +46,8 @@
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include <sys/stat.h>
 
 #include "../include/dentist_hip.h"
 
@@ -1079,6 +1085,180 @@ static int tool_stretcher(const std::vector<std::string> &args)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- fm-index
+// The contract is the reference program's (external/fm-index.cpp), restated: records and queries are lines; record ids are
+// 0-based line numbers, empty lines included; empty query lines are skipped and do not advance the 0-based query id, which
+// restarts for every source; per query all forward occurrences ascending by (record, begin), then with -r those of the
+// reverse complement; coordinates 0-based, right-open, relative to the record.  Deviations: no index is built --
+// <reference>.fm9 is a small file of our own that says so (check-results asserts that it exists, checkResults.d:684), and
+// <reference>.idx is not written; a last line without '\n' is a record (the reference program throws on a hit in it);
+// the alphabet is acgt, or ACGT if every letter of the reference and of all queries is upper case -- any other byte, or
+// mixed case, ends the run (the reference program matches bytes, so nothing is case-folded silently).
+namespace {
+const char kFm9Magic[8] = {'d', 'h', 'f', 'm', '9', '\n', 0, 0};
+const int64_t kFm9Version = 1;
+
+struct FmLetters {  // the case of the first letter seen, and where
+    int upper = -1;
+    std::string file;
+    long long line = 0;
+};
+
+// the lines of `text` as codes appended to `seq`, their ends to `off`; keep_empty: empty lines are records
+void fm_lines(const std::string &text, const std::string &file, bool keep_empty, FmLetters &lt, std::vector<uint8_t> &seq,
+              std::vector<int64_t> &off, std::vector<int64_t> *text_starts)
+{
+    long long line = 1;
+    size_t p = 0;
+    while (p < text.size()) {
+        size_t eol = text.find('\n', p);
+        const bool last_open = eol == std::string::npos;
+        if (last_open) eol = text.size();
+        if (text_starts) text_starts->push_back((int64_t)p);
+        for (size_t k = p; k < eol; k++) {
+            const unsigned char c = (unsigned char)text[k];
+            const unsigned char l = (unsigned char)(c | 32);
+            const bool letter = (c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z');
+            if (!letter || (l != 'a' && l != 'c' && l != 'g' && l != 't')) {
+                char msg[256];
+                snprintf(msg, sizeof(msg), "%s: line %lld: byte 0x%02x%s is not one of acgt (or ACGT)", file.c_str(), line, c,
+                         c == 'n' || c == 'N' ? " (n)" : "");
+                die(msg, 2);
+            }
+            const int upper = c < 'a';
+            if (lt.upper < 0) {
+                lt.upper = upper;
+                lt.file = file;
+                lt.line = line;
+            } else if (lt.upper != upper) {
+                char msg[512];
+                snprintf(msg, sizeof(msg), "%s: line %lld: %s-case letter, but %s line %lld is %s case: bytes are matched as they are, mixed "
+                         "case is refused", file.c_str(), line, upper ? "upper" : "lower", lt.file.c_str(), lt.line, lt.upper ? "upper" : "lower");
+                die(msg, 2);
+            }
+            seq.push_back((uint8_t)(l == 'a' ? 0 : l == 'c' ? 1 : l == 'g' ? 2 : 3));
+        }
+        if (keep_empty || eol > p) off.push_back((int64_t)seq.size());
+        p = eol + 1;
+        line++;
+    }
+}
+
+bool fm9_current(const std::string &path, int64_t size)
+{
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    char magic[8];
+    int64_t head[2] = {0, 0};
+    const bool ok = fread(magic, 1, 8, f) == 8 && fread(head, 8, 2, f) == 2 && memcmp(magic, kFm9Magic, 8) == 0 &&
+                    head[0] == kFm9Version && head[1] == size;
+    fclose(f);
+    return ok;
+}
+}  // namespace
+
+static int tool_fm_index(const std::vector<std::string> &args)
+{
+    auto usage = [](const std::string &err) {
+        fprintf(stderr,
+                "error: %s\n\nUsage fm-index [-P<dir>] [-r] <in:reference> [<in:queries> ...]\n"
+                "    Locates every exact occurrence of the <queries> (one per line) in <reference>\n"
+                "    (one record per line) on the GPU; reads standard input if no <queries> is given.\n\n"
+                "    -P<dir>   temporary directory (must exist; unused)\n"
+                "    -r        search the reverse complement of each query as well\n\n"
+                "    Output, TAB-separated: refName refId refLength queryId hitBegin hitEnd revComp\n"
+                "    Ids and coordinates are zero-based, coordinates right-open.  Leaves <reference>.fm9.\n",
+                err.c_str());
+        return 1;
+    };
+    bool both = false;
+    std::string tmpdir;
+    size_t i = 0;
+    for (; i < args.size() && !args[i].empty() && args[i][0] == '-'; i++) {
+        const std::string &a = args[i];
+        if (a.size() >= 2 && a[1] == 'P') {
+            tmpdir = a.substr(2);
+            if (tmpdir.empty()) return usage("Missing value for -P.");
+        } else if (a == "-r")
+            both = true;
+        else if (a.size() >= 2 && a[1] == 'r')
+            return usage("Flag -r takes no value.");
+        else
+            return usage("Invalid option " + a + ".");
+    }
+    if (!tmpdir.empty()) {
+        struct stat sb;
+        if (stat(tmpdir.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode)) return usage("Cannot open temporary directory: " + tmpdir);
+    }
+    if (i >= args.size()) return usage("Missing arguments.");
+    const std::string ref_path = args[i];
+    const std::vector<std::string> qfiles(args.begin() + (long)i + 1, args.end());
+    // ---- the reference: records, alphabet, <reference>.fm9
+    FILE *f = fopen(ref_path.c_str(), "rb");
+    if (!f) die("File `" + ref_path + "` does not exist.", 2);
+    const std::string ref_text = slurp(f);
+    fclose(f);
+    FmLetters lt;
+    std::vector<uint8_t> rseq, qseq;
+    std::vector<int64_t> roff{0}, qoff{0}, text_starts;
+    fm_lines(ref_text, ref_path, true, lt, rseq, roff, &text_starts);
+    text_starts.push_back((int64_t)ref_text.size());
+    const int64_t nref = (int64_t)roff.size() - 1;
+    const std::string fm9 = ref_path + ".fm9";
+    if (!fm9_current(fm9, (int64_t)ref_text.size())) {
+        fprintf(stderr, "{\"level\":\"info\",\"info\":\"Writing the record list (no index is needed).\",\"file\":\"%s\"}\n", fm9.c_str());
+        FILE *o = fopen(fm9.c_str(), "wb");
+        if (!o) die("cannot write " + fm9, 2);
+        const int64_t head[3] = {kFm9Version, (int64_t)ref_text.size(), nref};
+        const bool ok = fwrite(kFm9Magic, 1, 8, o) == 8 && fwrite(head, 8, 3, o) == 3 &&
+                        fwrite(text_starts.data(), 8, text_starts.size(), o) == text_starts.size();
+        if (fclose(o) != 0 || !ok) die("write error on " + fm9, 2);
+    }
+    // ---- the queries of every source
+    struct Source {
+        std::string name;
+        int64_t first;  // its first query in the call
+    };
+    std::vector<Source> sources;
+    auto add_source = [&](const std::string &name, const std::string &text) {
+        sources.push_back(Source{name, (int64_t)qoff.size() - 1});
+        fm_lines(text, name, false, lt, qseq, qoff, nullptr);
+    };
+    if (qfiles.empty())
+        add_source("stdin", slurp(stdin));
+    else
+        for (const std::string &q : qfiles) {
+            FILE *qf = fopen(q.c_str(), "rb");
+            if (!qf) {
+                fprintf(stderr, "{\"level\":\"warning\",\"info\":\"File does not exist. Skipping.\",\"file\":\"%s\"}\n", q.c_str());
+                continue;
+            }
+            add_source(q, slurp(qf));
+            fclose(qf);
+        }
+    const int64_t nqry = (int64_t)qoff.size() - 1;
+    dh_ctx *ctx = nullptr;
+    CHK(dh_ctx_create(0, nullptr, &ctx));
+    dh_exact_hits *hits = nullptr;
+    CHK(dh_exact_locate(ctx, rseq.data(), roff.data(), nref, qseq.data(), qoff.data(), nqry, both ? 1 : 0, &hits));
+    const dh_exact_hit *h = dh_exact_hits_records(hits);
+    const int64_t nh = dh_exact_hits_count(hits);
+    size_t s = 0;
+    std::string line;
+    for (int64_t k = 0; k < nh; k++) {
+        while (s + 1 < sources.size() && h[k].query >= sources[s + 1].first) s++;
+        char buf[160];
+        snprintf(buf, sizeof(buf), "\t%d\t%lld\t%lld\t%lld\t%lld\t%s\n", h[k].ref, (long long)(roff[(size_t)h[k].ref + 1] - roff[(size_t)h[k].ref]),
+                 (long long)(h[k].query - sources[s].first), (long long)h[k].begin, (long long)h[k].end, h[k].complement ? "yes" : "no");
+        line = sources[s].name + buf;
+        if (fwrite(line.data(), 1, line.size(), stdout) != line.size()) die("write error", 2);
+    }
+    if (fflush(stdout) != 0) die("write error", 2);
+    dh_exact_hits_destroy(hits);
+    dh_ctx_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     g_tool = argv[0];
@@ -1110,6 +1290,7 @@ int main(int argc, char **argv)
     if (g_tool == "LAtranspose") return tool_latranspose(args);
     if (g_tool == "DBnw") return tool_dbnw(args);
     if (g_tool == "stretcher") return tool_stretcher(args);
+    if (g_tool == "fm-index") return tool_fm_index(args);
     die("unknown tool (expected fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv "
         "computeintrinsicqv daccord merge-insertions)");
     return 1;
