@@ -71,7 +71,8 @@ SYMBOLS = [
     "dh_last_error", "dh_abi_version", "dh_ctx_create", "dh_ctx_destroy", "dh_ctx_sync",
     "dh_default_align_opts", "dh_db_create", "dh_db_destroy", "dh_db_drop_cache", "dh_db_nreads",
     "dh_db_total_bases", "dh_la_set_destroy", "dh_la_set_count", "dh_la_set_trace_len",
-    "dh_la_set_records", "dh_la_set_trace", "dh_la_set_tspace", "dh_get_align_stats", "dh_get_cum_stats", "dh_get_mjoin_counts", "dh_ctx_release_scratch",
+    "dh_la_set_records", "dh_la_set_trace", "dh_la_set_tspace", "dh_get_align_stats", "dh_get_cum_stats", "dh_get_mjoin_counts", "dh_get_join_counts", "dh_join_hit_capacity",
+    "dh_ctx_release_scratch",
     "dh_align_db",
     "dh_las_write", "dh_las_read", "dh_default_process_opts", "dh_collect_spanning", "dh_pileups_destroy",
     "dh_pileups_count", "dh_pileups_get", "dh_process_pileups", "dh_insertions_destroy",
@@ -250,6 +251,20 @@ def _check(rc):
         raise DhError(rc, lib().dh_last_error().decode(errors="replace"))
 
 
+def join_hit_capacity(bases, reads, skip_self=2, rate=0.0, free_bytes=-1):
+    """dh_join_hit_capacity: the hits the first attempt of the pile-up join makes room for.  bases / reads: per group;
+    rate <= 0: the figure a fresh context starts with; free_bytes < 0: no memory clamp.  Host arithmetic, no device."""
+    b = np.ascontiguousarray(bases, dtype=np.int64)
+    r = np.ascontiguousarray(reads, dtype=np.int32)
+    if b.shape != r.shape or b.ndim != 1:
+        raise ValueError("bases and reads: one entry per group each")
+    L = lib()
+    L.dh_join_hit_capacity.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                       ctypes.c_int64]
+    L.dh_join_hit_capacity.restype = ctypes.c_int64
+    return int(L.dh_join_hit_capacity(b.ctypes.data, r.ctypes.data, len(b), int(skip_self), float(rate), int(free_bytes)))
+
+
 def default_align_opts(**kw):
     o = AlignOpts()
     lib().dh_default_align_opts(ctypes.byref(o))
@@ -344,6 +359,14 @@ class Context:
         lib().dh_get_mjoin_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
         _check(lib().dh_get_mjoin_counts(self._h, out, int(reset)))
         return int(out[0]), int(out[1])
+
+    def join_counts(self, reset=False):
+        """(k_join launches, reruns among them, hits of the last join, capacity of its first attempt) of this context's
+        pile-up joins; after process_pileups the last two are sums over the concurrent parts of that call."""
+        out = (ctypes.c_int64 * 4)()
+        lib().dh_get_join_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
+        _check(lib().dh_get_join_counts(self._h, out, int(reset)))
+        return tuple(int(x) for x in out)
 
     def cum_stats(self, reset=False):
         st = CumStats()

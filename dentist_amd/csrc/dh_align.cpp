@@ -538,6 +538,30 @@ static int alloc_scratch(AlignRun &r)
     return DH_OK;
 }
 
+// the capacity (hits) of the first attempt of the pile-up join: rate x margin x sum over groups of bases x reads (see
+// DH_JOIN_HIT_RATE0, dh_internal.h), twice that when both directions of a pair are hits (skip_self other than 2); never
+// below what every call got before depth was looked at -- max(2^20, 1.25 x bases): a call that fitted then fits now --
+// and, that floor apart, never above DH_JOIN_HIT_MEM_FRACTION of the free device memory
+extern "C" int64_t dh_join_hit_capacity(const int64_t *bases, const int32_t *reads, int32_t ngroups, int32_t skip_self,
+                                        double rate, int64_t free_bytes)
+{
+    if (!(rate > 0)) rate = DH_JOIN_HIT_RATE0;
+    int64_t total = 0;
+    double depth_bases = 0;
+    for (int32_t g = 0; bases && reads && g < ngroups; g++)
+        if (bases[g] > 0 && reads[g] > 0) {
+            total += bases[g];
+            depth_bases += (double)bases[g] * (double)reads[g];
+        }
+    const int64_t floor_cap = std::max<int64_t>(1 << 20, (int64_t)(1.25 * (double)total));
+    // (a first hit has 40 bits in a segtab word)
+    const double want = std::min(rate * depth_bases * (skip_self == 2 ? 1.0 : 2.0) * DH_JOIN_HIT_MARGIN, (double)(1ll << 39));
+    int64_t cap = std::max(floor_cap, (int64_t)want);
+    if (free_bytes >= 0)
+        cap = std::min(cap, std::max(floor_cap, (int64_t)(DH_JOIN_HIT_MEM_FRACTION * (double)free_bytes) / (int64_t)sizeof(uint64_t)));
+    return cap;
+}
+
 // the pile-up join: one upload of the plan tables, k_join_part, then k_join until its hits fit (r.jv); a slice that
 // overflows its LDS table sends the whole call to the directory path (r.use_join = false, the index rebuilt)
 static int build_join(AlignRun &r, const JoinPlan &jp)
@@ -596,38 +620,73 @@ static int build_join(AlignRun &r, const JoinPlan &jp)
     HIPCHK(hipEventRecord(ctx->ev[6], st));
     dhk_join_part(st, jv, r.bv, o.k, o.kmer_mod);
     HIPCHK(hipGetLastError());
-    // hit buffer: measured 0.77 hits per base for pile-ups of 60 reads at 13 % error; a rerun sizes it exactly
-    int64_t hcap = std::max<int64_t>(1 << 20, (int64_t)(1.25 * (double)A->total));
+    // hit buffer: sized by pile-up depth with the rate this context has learned (dh_join_hit_capacity); a join whose hits
+    // do not fit leaves the size it needs in the cursor and is rerun with exactly that
+    std::vector<int64_t> gbases(ng);
+    std::vector<int32_t> greads(ng);
+    double depth_bases = 0;
+    for (size_t g = 0; g < ng; g++) {
+        const int32_t r0 = jp.gfirst[g], r1 = jp.gfirst[g + 1];
+        gbases[g] = A->h_off[(size_t)r1] - A->h_off[(size_t)r0];
+        greads[g] = r1 - r0;
+        depth_bases += (double)gbases[g] * (double)greads[g];
+    }
+    if (o.skip_self != 2) depth_bases *= 2.0;  // both directions of a pair are hits
+    int64_t hcap = dh_join_hit_capacity(gbases.data(), greads.data(), (int32_t)ng, o.skip_self, ctx->join_hit_rate, -1);
+    const size_t have = ctx->arena[SLOT_JOIN_HITS].cap / sizeof(uint64_t);
+    if ((size_t)hcap > have) {  // the buffer has to grow: no more than its share of the memory that is free now
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        const int64_t clamped = dh_join_hit_capacity(gbases.data(), greads.data(), (int32_t)ng, o.skip_self, ctx->join_hit_rate,
+                                                     (int64_t)free_b);
+        hcap = std::max(clamped, std::min(hcap, (int64_t)have));
+    }
     if (const char *e = getenv("DH_JOIN_HITCAP")) hcap = std::max<int64_t>(1, atoll(e));  // development / tests
-    for (int attempt = 0;; attempt++) {
+    ctx->join_first_cap = hcap;
+    int attempt = 0;
+    for (;; attempt++) {
         SCR(SLOT_JOIN_HITS, d_hits, (size_t)hcap)
         jv.hits = d_hits;
         jv.hits_cap = hcap;
         HIPCHK(hipMemsetAsync(d_cursor, 0, sizeof(unsigned long long), st));
         dhk_join(st, jv, r.bv, r.dopt, A->ix.d_goff, r.sepv);
         HIPCHK(hipGetLastError());
-        unsigned long long cur = 0;
+        ctx->join_launches++;
+        if (attempt > 0) ctx->join_reruns++;
+        // the histogram reads segtab only, which k_join fills whether the hits fitted or not: it goes right behind, and
+        // cursor, histogram and status come back in one wait (a join that is rerun or abandoned discards the histogram)
+        dhk_join_hist(st, jv, B->d_group, B->n, (unsigned int *)(d_cursor + 1));
+        HIPCHK(hipGetLastError());
+        struct {
+            unsigned long long cur;
+            unsigned int hist[4];
+        } back = {0, {0, 0, 0, 0}};
+        static_assert(sizeof(back) == 3 * sizeof(unsigned long long), "cursor and histogram words are one copy");
         int32_t jstatus = 0;
-        HIPCHK(hipMemcpyAsync(&cur, d_cursor, sizeof(cur), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&back, d_cursor, sizeof(back), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(&jstatus, r.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipEventRecord(ctx->ev[7], st));
         HIPCHK(hipStreamSynchronize(st));
-        r.join_hits = (int64_t)cur;
+        r.join_hits = (int64_t)back.cur;
         if (jstatus & DH_ST_JOIN_OVERFLOW) {  // a slice did not fit its LDS table: directory path for this call
             r.use_join = false;
             break;
         }
-        if (!(jstatus & DH_ST_JOIN_HITCAP)) break;
+        ctx->join_last_hits = (int64_t)back.cur;
+        if (depth_bases > 0) ctx->join_hit_rate = std::max(ctx->join_hit_rate, (double)back.cur / depth_bases);
+        if (!(jstatus & DH_ST_JOIN_HITCAP)) {
+            memcpy(r.jhist, back.hist, sizeof(r.jhist));
+            break;
+        }
         if (attempt >= 2) return fail(DH_EOVERFLOW, "k-mer join: hit buffer capacity exceeded twice");
-        hcap = (int64_t)cur + 1024;
+        hcap = (int64_t)back.cur + 1024;
         HIPCHK(hipMemsetAsync(r.d_status, 0, sizeof(int32_t), st));
     }
-    if (r.use_join) {
-        dhk_join_hist(st, jv, B->d_group, B->n, (unsigned int *)(d_cursor + 1));
-        HIPCHK(hipMemcpyAsync(r.jhist, d_cursor + 1, sizeof(unsigned int) * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipEventRecord(ctx->ev[7], st));
-    HIPCHK(hipEventSynchronize(ctx->ev[7]));
     HIPCHK(hipEventElapsedTime(&r.ms_join, ctx->ev[6], ctx->ev[7]));
+    if (getenv("DH_TRACE"))
+        fprintf(stderr, "[join] hit buffer %lld (%.1f MB), %lld hits, %d attempt(s); %.4f hits per base per read of depth from now on\n",
+                (long long)ctx->join_first_cap, (double)ctx->join_first_cap * sizeof(uint64_t) / 1048576.0, (long long)r.join_hits,
+                attempt + 1, ctx->join_hit_rate);
     if (!r.use_join) {
         if (getenv("DH_TRACE")) fprintf(stderr, "[join] a slice overflowed its table: falling back to the k-mer directory\n");
         HIPCHK(hipMemsetAsync(r.d_status, 0, sizeof(int32_t), st));

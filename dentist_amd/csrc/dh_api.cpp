@@ -148,6 +148,17 @@ extern "C" int dh_get_mjoin_counts(dh_ctx *c, int64_t *out2, int32_t reset)
     return DH_OK;
 }
 
+extern "C" int dh_get_join_counts(dh_ctx *c, int64_t *out4, int32_t reset)
+{
+    if (!c || !out4) return fail(DH_EINVAL, "dh_get_join_counts: NULL");
+    out4[0] = c->join_launches;
+    out4[1] = c->join_reruns;
+    out4[2] = c->join_last_hits;
+    out4[3] = c->join_first_cap;
+    if (reset) c->join_launches = c->join_reruns = c->join_last_hits = c->join_first_cap = 0;
+    return DH_OK;
+}
+
 extern "C" int dh_get_align_stats(dh_ctx *c, dh_align_stats *out)
 {
     if (!c || !out) return fail(DH_EINVAL, "dh_get_align_stats: NULL");

@@ -134,6 +134,17 @@ enum DhSlot : int {
 enum { DH_STW_STATUS = 0, DH_STW_PACK = 1, DH_STW_PACK_RC = 2, DH_STW_COUNT = 4 };
 static_assert(DH_STW_PACK_RC == DH_STW_PACK + 1, "chunk_copies clears the two flag words with one memset");
 
+// The hit buffer of the pile-up join (build_join, dh_align.cpp) is sized by pile-up depth.  Every template position has
+// about n p intact copies among the n reads of a pile-up (p: a k-mer survives the errors), every unordered pair of copies
+// is one hit, a group has n L bases: n p^2 / 2 hits per base, i.e. a constant per base PER READ OF DEPTH.  Measured at 13 %
+// error, k = 14: 0.77 hits per base at 60 reads (0.0128 per read of depth), 1.94 at 166 (0.0117) -- the larger one starts a
+// context.  The margin covers depth and cropped length varying between the pile-ups of one call.
+#define DH_JOIN_HIT_RATE0 0.0128
+#define DH_JOIN_HIT_MARGIN 1.5
+// ... and the buffer never takes more than this fraction of the device memory free at that moment (three concurrent parts
+// of the process stage size theirs side by side); above it the rerun with the exact size stays the way out
+#define DH_JOIN_HIT_MEM_FRACTION 0.25
+
 struct dh_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -149,6 +160,10 @@ struct dh_ctx {
     double mj_hit_frac = 0.2;  // hits per sampled k-mer the hit pool of the partitioned join is sized for (raised when a pool overflowed)
     int seed_wave_tier = 1;  // the wavefront-per-read first tier of the segment-fed seed back end (0: most reads overflowed it)
     int64_t mj_chunks = 0, mj_fallbacks = 0;  // chunks seeded by the partitioned join / redone by the directory (dh_get_mjoin_counts)
+    // the pile-up join's hit buffer (build_join): hits per base per read of depth it is sized for -- raised to what a join
+    // produced, never lowered (a capacity hint: results do not depend on it) -- and dh_get_join_counts' four counters
+    double join_hit_rate = DH_JOIN_HIT_RATE0;
+    int64_t join_launches = 0, join_reruns = 0, join_last_hits = 0, join_first_cap = 0;
     int32_t near_best_ppm = -1;  // damapper -n of this context (dh_ctx_set_near_best); -1 = the process default
     // second context of the same device (own streams and scratch), created on first use: the process stage runs the
     // two halves of a batch of pile-ups concurrently, one on each (dh_process_pileups)

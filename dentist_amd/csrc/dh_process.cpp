@@ -1872,6 +1872,13 @@ extern "C" int dh_process_pileups_masked(dh_ctx *ctx, dh_db *contigs, dh_db *rea
         a.wave_launches += b.wave_launches; a.wave_cells += b.wave_cells; a.alignments += b.alignments; a.las += b.las;
         a.aligned_bp += b.aligned_bp; a.trace_values += b.trace_values; a.hits += b.hits; a.b_bases += b.b_bases;
         b = dh_cum_stats();
+        // ... and so do their pile-up joins (dh_get_join_counts: hits and first capacity of the call are sums over its parts)
+        dh_ctx *sc = ctx->sub[k - 1];
+        ctx->join_launches += sc->join_launches;
+        ctx->join_reruns += sc->join_reruns;
+        ctx->join_last_hits += sc->join_last_hits;
+        ctx->join_first_cap += sc->join_first_cap;
+        sc->join_launches = sc->join_reruns = sc->join_last_hits = sc->join_first_cap = 0;
     }
     for (int32_t k = 0; k < nparts; k++)
         if (rcs[(size_t)k]) {

@@ -159,6 +159,16 @@ int dh_ctx_release_scratch(dh_ctx *ctx);
  * and chunks that exceeded one of its capacities and were redone by the directory lookups -- out2[1].  Both paths give
  * the same alignments; the counts say which one ran (tests, traces). */
 int dh_get_mjoin_counts(dh_ctx *ctx, int64_t *out2, int32_t reset);
+/* The pile-up join (csrc/dh_join.h) of the grouped all-vs-all calls on this context: out4[0] k_join launches, out4[1] those
+ * of them that were reruns (the hit buffer of the launch before was too small), out4[2] the hits of the last join, out4[3]
+ * the capacity (hits) its first attempt ran with.  After dh_process_pileups the counters of its concurrent parts are added
+ * to the context's: out4[2] and out4[3] are then sums over the parts of that call.  reset clears all four. */
+int dh_get_join_counts(dh_ctx *ctx, int64_t *out4, int32_t reset);
+/* The capacity (hits) that join's first attempt asks for -- host arithmetic only, no device needed.  bases[g] / reads[g]:
+ * bases and reads of group g; rate: hits per base per read of depth (<= 0: the initial figure of a fresh context);
+ * free_bytes: device memory free at that moment (< 0: not known, no clamp).  See dh_join_hit_capacity in csrc/dh_join.h. */
+int64_t dh_join_hit_capacity(const int64_t *bases, const int32_t *reads, int32_t ngroups, int32_t skip_self, double rate,
+                             int64_t free_bytes);
 
 /*
  * dh_align_db -- every sequence of B against all of A: k-mer seeds, diagonal band filter, wave
