@@ -86,3 +86,11 @@ tests/native/liblocate_host.so: tests/native/locate_host.cpp dentist_amd/csrc/dh
 # after a change to dh_locate.h -- the two-word loads at the end of the packed text are where this code would overrun
 tests/native/locate_host_san: tests/native/locate_host_main.cpp tests/native/locate_host.cpp dentist_amd/csrc/dh_locate.h
 	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -Wno-unknown-pragmas -o $@ tests/native/locate_host_main.cpp tests/native/locate_host.cpp
+
+# the slot code of the per-group table join (dentist_amd/csrc/dh_tjoin.h) compiled for the CPU: test infrastructure
+tests/native/libtjoin_host.so: tests/native/tjoin_host.cpp dentist_amd/csrc/dh_tjoin.h
+	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -o $@ $<
+
+# the same harness and a stand-alone main under the host sanitizers (a program of its own: nothing is preloaded)
+tests/native/tjoin_host_san: tests/native/tjoin_host_main.cpp tests/native/tjoin_host.cpp dentist_amd/csrc/dh_tjoin.h
+	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/tjoin_host_main.cpp tests/native/tjoin_host.cpp

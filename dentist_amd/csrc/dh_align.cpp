@@ -15,6 +15,7 @@
 #include "dh_internal.h"
 #include "dh_join.h"
 #include "dh_mjoin.h"
+#include "dh_tjoin.h"
 #include "dh_tile.h"
 #include "dh_parallel.h"
 
@@ -236,7 +237,7 @@ struct AlignRun {
     Tasks tasks;
     dh_align_stats stats = {};
     // derived flags
-    bool tiled, use_join = false, use_mj = false, db_copies = false, want_packed = false, dual = false, sym_tiled = false,
+    bool tiled, use_join = false, use_mj = false, use_tj = false, db_copies = false, want_packed = false, dual = false, sym_tiled = false,
          keep_dev = false;
     // geometry: items of the call, per chunk (cn), capacities of the extension
     int64_t nitems_total, item_first, item_end;
@@ -697,6 +698,11 @@ static int build_join(AlignRun &r, const JoinPlan &jp)
 }
 
 // the LDS hit capacity of the seed filter; whether the mapping goes by the partitioned join (and its presence bitmap)
+static void ctx_count_tj_fallback(dh_ctx *ctx)
+{
+    ctx->tj_fallbacks++;
+    if (getenv("DH_TRACE")) fprintf(stderr, "[tjoin] a limit of the table join is not met: this call keeps the k-mer directory\n");
+}
 static int plan_seeds(AlignRun &r)
 {
     dh_db *A = r.A, *B = r.B;
@@ -743,6 +749,24 @@ static int plan_seeds(AlignRun &r)
         dhk_mj_bitmap(r.st, A->ix.d_ent, A->ix.n, o.k, nbbits, A->ix.d_bitmap);
         HIPCHK(hipGetLastError());
         A->ix.nbbits = nbbits;
+    }
+    // ---- a grouped A against a grouped B (the consensus re-alignment: templates against the reads of their pile-ups): a
+    // read only meets the index entries of its own group, which k_tjoin (dh_tjoin.h) holds in LDS -- bit-identical hits.
+    // A call that does not meet the limits keeps the directory and is counted; DH_NO_TJOIN=1 forces the directory,
+    // DH_TJOIN_CAP lowers the entries per group the table is planned for (tests: the fall-back).
+    if (!r.use_join && A != B && A->d_group && !getenv("DH_NO_TJOIN")) {
+        int64_t tcap_ent = TJ_CAP;
+        if (const char *e = getenv("DH_TJOIN_CAP")) tcap_ent = std::max<int64_t>(0, std::min<int64_t>(TJ_CAP, atoll(e)));
+        // (a group of B without sequences in A, beyond A's last group included, is an empty table to k_tjoin: its reads
+        // get no hits, which is what "no template in the pile-up" means; the group ids themselves are the callers' and
+        // are the same numbering on both sides)
+        r.use_tj = B->d_group && o.k <= TJ_MAXK && o.skip_self == 0 && A->ix.d_gent &&
+                   A->ix.max_gent <= tcap_ent && A->ix.n < (1ll << 31) && B->max_len < (1 << 24);
+        if (!r.use_tj) ctx_count_tj_fallback(r.ctx);
+        if (r.use_tj) {
+            r.ctx->tj_calls++;
+            r.ctx->tj_last_hits = 0;
+        }
     }
     return DH_OK;
 }
@@ -897,8 +921,82 @@ static int seed_chunk(AlignRun &r, AlignChunk &c, bool *redo)
         jv_mj.read0 = mv.r0;
         mj_chunk = true;
     }
-    const bool jn = r.use_join || mj_chunk;            // the back end gathers its hits from segments
-    const JoinView &jvx = mj_chunk ? jv_mj : r.jv;
+    // the per-group table join: units (group, run of consecutive reads), count + reserve + write; a hit buffer that was
+    // too small is sized by what the cursor counted and the kernel runs again
+    JoinView jv_tj = {};
+    bool tj_chunk = false;
+    unsigned long long tj_hits = 0;
+    if (r.use_tj) {
+        const int32_t cr0 = (int32_t)(item0 >> 1), cr1 = (int32_t)((item0 + ni) >> 1);
+        std::vector<int4> units;
+        for (int32_t rd = cr0; rd < cr1;) {
+            const int32_t g = B->h_group[(size_t)rd];
+            int32_t e = rd + 1;
+            while (e < cr1 && e - rd < TJ_RUN && B->h_group[(size_t)e] == g) e++;
+            units.push_back(int4{g, rd, e, 0});
+            rd = e;
+        }
+        const int64_t cbases = B->h_off[(size_t)cr1] - B->h_off[(size_t)cr0];
+        // first attempt: the hits per base the context has seen (plus a quarter), exact from the cursor after that
+        int64_t hcap = (int64_t)(1.25 * ctx->tj_hit_rate * (double)cbases) + 4096;
+        if (const char *e = getenv("DH_TJOIN_HITCAP")) hcap = std::max<int64_t>(1, atoll(e));  // development / tests: force the rerun
+        TjView tv = {};
+        int4 *d_units;
+        uint32_t *d_tjctr;
+        SCR(SLOT_TJ_UNITS, d_units, units.size())
+        SCR(SLOT_TJ_SEGTAB, tv.segtab, (size_t)(cr1 - cr0))
+        SCR(SLOT_TJ_CTR, d_tjctr, 4)
+        HIPCHK(hipMemcpyAsync(d_units, units.data(), sizeof(int4) * units.size(), hipMemcpyHostToDevice, st));
+        tv.gent = r.A->ix.d_gent;
+        tv.ngroups = r.A->ngroups;
+        tv.units = d_units;
+        tv.nunits = (int32_t)units.size();
+        tv.read0 = cr0;
+        tv.cursor = (unsigned long long *)d_tjctr;
+        tv.queue = d_tjctr + 2;
+        tv.status = r.d_status;
+        int32_t tst = 0;
+        for (int attempt = 0;; attempt++) {
+            SCR(SLOT_TJ_HITS, tv.hits, (size_t)hcap)
+            tv.hits_cap = hcap;
+            HIPCHK(hipMemsetAsync(d_tjctr, 0, 4 * sizeof(uint32_t), st));
+            dhk_tjoin(st, r.bv, r.iv, r.dopt, tv, ctx->ncu);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&tj_hits, tv.cursor, sizeof(tj_hits), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(&tst, r.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));  // (units goes out of scope behind this)
+            if (!(tst & DH_ST_TJ_HITCAP)) break;
+            if (attempt > 0) return fail(DH_EOVERFLOW, "table join: the hit buffer sized by the count pass was too small");
+            tst &= ~DH_ST_TJ_HITCAP;
+            HIPCHK(hipMemcpyAsync(r.d_status, &tst, sizeof(int32_t), hipMemcpyHostToDevice, st));
+            if (getenv("DH_TRACE")) fprintf(stderr, "[tjoin] hit buffer of %lld too small for %llu hits: run again\n", (long long)hcap, tj_hits);
+            hcap = (int64_t)tj_hits;
+            ctx->tj_reruns++;
+        }
+        // the next first attempt goes by what this call produced, never below the starting figure: one low-error call
+        // (0.87 hits per base at 1 %) does not make every later buffer of the context six times larger at 8 bytes per
+        // hit -- a call after it that needs more than it left pays one rerun
+        if (cbases > 0) ctx->tj_hit_rate = std::max(DH_TJ_HIT_RATE0, (double)tj_hits / (double)cbases);
+        if (tst & DH_ST_TJ_OVERFLOW) {
+            // (a read with 2^24 hits or more: nothing the segment word can describe) the whole call by the directory
+            tst &= ~DH_ST_TJ_OVERFLOW;
+            HIPCHK(hipMemcpyAsync(r.d_status, &tst, sizeof(int32_t), hipMemcpyHostToDevice, st));
+            HIPCHK(hipStreamSynchronize(st));
+            r.use_tj = false;
+            ctx->tj_calls--;
+            ctx_count_tj_fallback(ctx);
+            *redo = true;
+            return DH_OK;
+        }
+        jv_tj.segtab = tv.segtab;
+        jv_tj.hits = tv.hits;
+        jv_tj.status = r.d_status;
+        jv_tj.ns_fixed = 1;
+        jv_tj.read0 = cr0;
+        tj_chunk = true;
+    }
+    const bool jn = r.use_join || mj_chunk || tj_chunk;  // the back end gathers its hits from segments
+    const JoinView &jvx = mj_chunk ? jv_mj : (tj_chunk ? jv_tj : r.jv);
     // (the back end fed from segments exists with 2048, 4096 and 8192 entries of LDS; the 8192-entry one scans in a slab)
     const int tier_max = getenv("DH_SEED_NO16K") ? 8192 : 16384;  // development / tests: without the 16384-entry tier
     // (a mapping chunk through the partitioned join starts with the wavefront-per-read tier: 512 hits, 32 candidate band
@@ -911,10 +1009,11 @@ static int seed_chunk(AlignRun &r, AlignChunk &c, bool *redo)
     // read).  The wavefront-per-read tier is switched off for the context once a quarter of a chunk's reads overflowed it.
     const double kmers_per_read = (double)(B->h_off[(size_t)((item0 + ni) >> 1)] - B->h_off[(size_t)(item0 >> 1)]) /
                                   std::max(1, ni / 2) / std::max(1, o.kmer_mod);
-    const double mean_hits = kmers_per_read * (2.0 * r.dens + 0.075);
-    const bool wave_tier = mj_chunk && ctx->seed_wave_tier && 1.5 * mean_hits <= 512.0 && !getenv("DH_SEED_NO_WAVE_TIER");
+    // (the table join has counted its hits: the mean is known)
+    const double mean_hits = tj_chunk ? (double)tj_hits / std::max(1, ni / 2) : kmers_per_read * (2.0 * r.dens + 0.075);
+    const bool wave_tier = (mj_chunk || tj_chunk) && ctx->seed_wave_tier && 1.5 * mean_hits <= 512.0 && !getenv("DH_SEED_NO_WAVE_TIER");
     int capj = std::min(std::max(r.cap, 2048), tier_max);
-    if (mj_chunk) {
+    if (mj_chunk || tj_chunk) {
         capj = 2048;
         while (capj < tier_max && 1.5 * mean_hits > capj) capj *= 2;
         if (wave_tier) capj = 512;
@@ -994,6 +1093,7 @@ static int seed_chunk(AlignRun &r, AlignChunk &c, bool *redo)
         return DH_OK;
     }
     if (mj_chunk) ctx->mj_chunks++;
+    if (tj_chunk) ctx->tj_last_hits += (int64_t)tj_hits;
     r.mj_skip_chunk = false;  // (the next chunk tries the join again)
     if (jn && capj < tier_max && !big.empty()) {
         // further tiers of the join path: the reads above the first capacity that fit the 8192-entry variant, then the

@@ -148,6 +148,17 @@ extern "C" int dh_get_mjoin_counts(dh_ctx *c, int64_t *out2, int32_t reset)
     return DH_OK;
 }
 
+extern "C" int dh_get_tjoin_counts(dh_ctx *c, int64_t *out4, int32_t reset)
+{
+    if (!c || !out4) return fail(DH_EINVAL, "dh_get_tjoin_counts: NULL");
+    out4[0] = c->tj_calls;
+    out4[1] = c->tj_fallbacks;
+    out4[2] = c->tj_last_hits;
+    out4[3] = c->tj_reruns;
+    if (reset) c->tj_calls = c->tj_fallbacks = c->tj_last_hits = c->tj_reruns = 0;
+    return DH_OK;
+}
+
 extern "C" int dh_get_join_counts(dh_ctx *c, int64_t *out4, int32_t reset)
 {
     if (!c || !out4) return fail(DH_EINVAL, "dh_get_join_counts: NULL");

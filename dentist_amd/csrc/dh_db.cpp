@@ -5,6 +5,7 @@
 #include <cstdlib>
 
 #include "dh_internal.h"
+#include "dh_tjoin.h"
 
 #define fail dh_fail
 
@@ -545,7 +546,19 @@ int dh_build_index(dh_db *A, int32_t k, int32_t sepv, int32_t kmer_mod, bool lig
     HIPCHK(dh_dev_alloc(&ix.d_fat, sizeof(ulonglong2) * (size_t)nb));
     dhk_fat_dir(ctx->stream, ix.d_dir, ix.d_ent, nb, ix.d_fat);
     HIPCHK(hipGetLastError());
+    // the per-group table join reads a group's entries as one range of the entry array: the group is the top key bits
+    // and the index lies in bucket order, so the range ends where the group's last bucket does (groups own whole buckets
+    // when the bucket shift leaves the group bits alone)
+    std::vector<uint32_t> gent;
+    if (A->d_group && ix.shift <= 2 * k) {
+        gent.resize((size_t)A->ngroups + 1);
+        HIPCHK(dh_dev_alloc(&ix.d_gent, sizeof(uint32_t) * gent.size()));
+        dhk_tj_group_offsets(ctx->stream, ix.d_dir, A->ngroups, k, ix.shift, nb, ix.d_gent);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(gent.data(), ix.d_gent, sizeof(uint32_t) * gent.size(), hipMemcpyDeviceToHost, ctx->stream));
+    }
     HIPCHK(hipStreamSynchronize(ctx->stream));  // tiles vector goes out of scope
+    for (size_t g2 = 0; g2 + 1 < gent.size(); g2++) ix.max_gent = std::max<int64_t>(ix.max_gent, (int64_t)gent[g2 + 1] - (int64_t)gent[g2]);
     dh_dev_free(d_tiles);
     dh_dev_free(d_sums);
     dh_dev_free(ix.d_dir_alloc);

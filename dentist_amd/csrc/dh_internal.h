@@ -98,6 +98,8 @@ enum DhSlot : int {
     // the mapping join (plan_mj_chunk, dh_align.cpp): planned per chunk, read by that chunk's seeds
     SLOT_MJ_ENT, SLOT_MJ_SEGOFF, SLOT_MJ_TILE_N, SLOT_MJ_TILE_R, SLOT_MJ_SEG, SLOT_MJ_HSEG, SLOT_MJ_HITS, SLOT_MJ_RHITS,
     SLOT_MJ_SEGTAB, SLOT_MJ_CTR,
+    // the per-group table join (seed_chunk, dh_align.cpp): the units, hit segments and hits of one chunk, read by its seeds
+    SLOT_TJ_UNITS, SLOT_TJ_SEGTAB, SLOT_TJ_HITS, SLOT_TJ_CTR,
     // the process rounds (the vote and emit pass of a consensus round, dh_process.cpp): live for one round
     SLOT_PR_VOFF, SLOT_PR_VOTES, SLOT_PR_OUT, SLOT_PR_STATUS, SLOT_PR_STAGE, SLOT_PR_SEGS, SLOT_PR_DECISIONS, SLOT_PR_CDIFF,
     // comm (dh_comm.cpp: the staging buffers of a collective): live for one collective; several requests (one per kind)
@@ -145,6 +147,8 @@ static_assert(DH_STW_PACK_RC == DH_STW_PACK + 1, "chunk_copies clears the two fl
 // of the process stage size theirs side by side); above it the rerun with the exact size stays the way out
 #define DH_JOIN_HIT_MEM_FRACTION 0.25
 
+#define DH_TJ_HIT_RATE0 0.14
+
 struct dh_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -160,6 +164,11 @@ struct dh_ctx {
     double mj_hit_frac = 0.2;  // hits per sampled k-mer the hit pool of the partitioned join is sized for (raised when a pool overflowed)
     int seed_wave_tier = 1;  // the wavefront-per-read first tier of the segment-fed seed back end (0: most reads overflowed it)
     int64_t mj_chunks = 0, mj_fallbacks = 0;  // chunks seeded by the partitioned join / redone by the directory (dh_get_mjoin_counts)
+    // the per-group table join (dh_tjoin.h; dh_get_tjoin_counts): calls seeded by it, grouped calls A != B that kept the
+    // directory because a limit was not met, hits of the last call, reruns of the hit buffer -- and the hits per base of B
+    // the buffer is sized for: 0.87^14 = 0.14 true seeds per base at k = 14 to start with, then what the last call produced
+    int64_t tj_calls = 0, tj_fallbacks = 0, tj_last_hits = 0, tj_reruns = 0;
+    double tj_hit_rate = DH_TJ_HIT_RATE0;
     // the pile-up join's hit buffer (build_join): hits per base per read of depth it is sized for -- raised to what a join
     // produced, never lowered (a capacity hint: results do not depend on it) -- and dh_get_join_counts' four counters
     double join_hit_rate = DH_JOIN_HIT_RATE0;
@@ -195,8 +204,15 @@ struct dh_index {
     uint32_t *d_bitmap = nullptr;
     int32_t nbbits = 0;
     bool light = false;  // virtual axis only (no directory): the hits come from the k-mer join (dh_join.hip)
+    // grouped A whose groups own whole buckets: first entry of every group (ngroups + 1 values, taken from the directory
+    // before it is released) for the per-group table join (dh_tjoin.h); max_gent: entries of the largest group
+    uint32_t *d_gent = nullptr;
+    int64_t max_gent = 0;
     void release()
     {
+        dh_dev_free(d_gent);
+        d_gent = nullptr;
+        max_gent = 0;
         dh_dev_free(d_dir_alloc);
         d_dir_alloc = nullptr;
         dh_dev_free(d_ent);

@@ -1879,6 +1879,12 @@ extern "C" int dh_process_pileups_masked(dh_ctx *ctx, dh_db *contigs, dh_db *rea
         ctx->join_last_hits += sc->join_last_hits;
         ctx->join_first_cap += sc->join_first_cap;
         sc->join_launches = sc->join_reruns = sc->join_last_hits = sc->join_first_cap = 0;
+        // ... and the table joins of their re-alignment rounds (dh_get_tjoin_counts)
+        ctx->tj_calls += sc->tj_calls;
+        ctx->tj_fallbacks += sc->tj_fallbacks;
+        ctx->tj_last_hits += sc->tj_last_hits;
+        ctx->tj_reruns += sc->tj_reruns;
+        sc->tj_calls = sc->tj_fallbacks = sc->tj_last_hits = sc->tj_reruns = 0;
     }
     for (int32_t k = 0; k < nparts; k++)
         if (rcs[(size_t)k]) {

@@ -164,6 +164,13 @@ int dh_get_mjoin_counts(dh_ctx *ctx, int64_t *out2, int32_t reset);
  * the capacity (hits) its first attempt ran with.  After dh_process_pileups the counters of its concurrent parts are added
  * to the context's: out4[2] and out4[3] are then sums over the parts of that call.  reset clears all four. */
 int dh_get_join_counts(dh_ctx *ctx, int64_t *out4, int32_t reset);
+/* The per-group table join (csrc/dh_tjoin.h) of the calls of a grouped A against a grouped B on this context (the
+ * consensus re-alignment: templates against the reads of their pile-ups): out4[0] calls whose seeds came from the group's
+ * k-mer table on chip, out4[1] such calls that kept the directory lookups because a limit was not met (a group with more
+ * index entries than the table is planned for, k > 16, B not grouped), out4[2] the hits of the last call, out4[3] reruns of
+ * the hit buffer.  After dh_process_pileups the counters of its concurrent parts are added to the context's.  Both paths
+ * give the same alignments.  reset clears all four. */
+int dh_get_tjoin_counts(dh_ctx *ctx, int64_t *out4, int32_t reset);
 /* The capacity (hits) that join's first attempt asks for -- host arithmetic only, no device needed.  bases[g] / reads[g]:
  * bases and reads of group g; rate: hits per base per read of depth (<= 0: the initial figure of a fresh context);
  * free_bytes: device memory free at that moment (< 0: not known, no clamp).  See dh_join_hit_capacity in csrc/dh_join.h. */
