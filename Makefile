@@ -6,7 +6,7 @@ CSRC := dentist_amd/csrc
 LIB := dentist_amd/libdentist_hip.so
 SIM := dentist_amd/sim/libdh_sim.so
 
-DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index
+DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index chain-local-alignments
 TOOLS := tools/daligner tools/damapper tools/datander tools/dazz_tools $(addprefix tools/,$(DAZZ_TOOLS))
 
 all: $(LIB) $(SIM) oracle $(TOOLS)
@@ -94,3 +94,12 @@ tests/native/libtjoin_host.so: tests/native/tjoin_host.cpp dentist_amd/csrc/dh_t
 # the same harness and a stand-alone main under the host sanitizers (a program of its own: nothing is preloaded)
 tests/native/tjoin_host_san: tests/native/tjoin_host_main.cpp tests/native/tjoin_host.cpp dentist_amd/csrc/dh_tjoin.h
 	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/tjoin_host_main.cpp tests/native/tjoin_host.cpp
+
+# the lane code and the host plan of the chaining (dentist_amd/csrc/dh_chain.h) compiled for the CPU: test infrastructure
+tests/native/libchain_host.so: tests/native/chain_host.cpp dentist_amd/csrc/dh_chain.h include/dentist_hip.h
+	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -o $@ $<
+
+# the same harness and a stand-alone main under the host sanitizers (a program of its own: nothing is preloaded); run it once
+# after a change to dh_chain.h
+tests/native/chain_host_san: tests/native/chain_host_main.cpp tests/native/chain_host.cpp dentist_amd/csrc/dh_chain.h include/dentist_hip.h
+	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/chain_host_main.cpp tests/native/chain_host.cpp

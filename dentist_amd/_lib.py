@@ -53,6 +53,12 @@ class ProcessOpts(ctypes.Structure):
         "max_partners", "min_relative_score_ppm")]
 
 
+class ChainOpts(ctypes.Structure):
+    """dh_chain_opts (ChainingOptions of the reference): 32 bytes"""
+    _fields_ = [("max_indel", ctypes.c_int32), ("max_chain_gap", ctypes.c_int32), ("min_score", ctypes.c_int32),
+                ("pad_", ctypes.c_int32), ("max_relative_overlap", ctypes.c_double), ("min_relative_score", ctypes.c_double)]
+
+
 INSERTION_DTYPE = np.dtype([(n, "<i4") for n in (
     "contig_left", "status", "nreads", "ref_read", "ref_read_id", "crop_left", "crop_right", "left_aepos",
     "right_abpos", "ins_begin", "ins_end", "comp", "cons_len", "left_diffs", "right_diffs", "join")]
@@ -105,6 +111,9 @@ SYMBOLS = [
     "dh_edit_paths_general_tiles", "dh_format_cigar", "dh_format_alignment", "dh_la_transpose", "dh_la_set_transpose",
     "dh_nw_batch", "dh_nw_affine_batch", "dh_format_pair",
     "dh_exact_locate", "dh_exact_hits_destroy", "dh_exact_hits_count", "dh_exact_hits_records",
+    "dh_default_chain_opts", "dh_la_chain", "dh_la_set_chain", "dh_la_chains_destroy", "dh_la_chains_count", "dh_la_chains_records",
+    "dh_la_chains_off", "dh_la_chains_score", "dh_la_chains_src_index", "dh_la_chains_flags", "dh_la_chains_big_pairs",
+    "dh_la_chains_to_set",
 ]
 
 _LIB = None
@@ -242,6 +251,19 @@ def lib():
     L.dh_exact_hits_count.restype = i64
     L.dh_exact_hits_records.argtypes = [vp]
     L.dh_exact_hits_records.restype = vp
+    L.dh_default_chain_opts.argtypes = [ctypes.POINTER(ChainOpts), i32]
+    L.dh_default_chain_opts.restype = None
+    L.dh_la_chain.argtypes = [vp, vp, i64, ctypes.POINTER(ChainOpts), ctypes.POINTER(vp)]
+    L.dh_la_set_chain.argtypes = [vp, vp, ctypes.POINTER(ChainOpts), ctypes.POINTER(vp)]
+    L.dh_la_chains_destroy.argtypes = [vp]
+    L.dh_la_chains_destroy.restype = None
+    for name in ("count", "records", "big_pairs"):
+        getattr(L, "dh_la_chains_" + name).argtypes = [vp]
+        getattr(L, "dh_la_chains_" + name).restype = i64
+    for name in ("off", "score", "src_index", "flags"):
+        getattr(L, "dh_la_chains_" + name).argtypes = [vp]
+        getattr(L, "dh_la_chains_" + name).restype = vp
+    L.dh_la_chains_to_set.argtypes = [vp, vp, i64, vp, i32, ctypes.POINTER(vp)]
     _LIB = L
     return L
 
@@ -519,6 +541,15 @@ class Context:
             L.dh_exact_hits_destroy(h)
         return out
 
+    def chain(self, las, tspace=None, **opts):
+        """dh_la_chain: chainLocalAlignments on records sorted by (aread, bread).  tspace: the trace spacing, the default of
+        min_score (100 when omitted); opts: fields of ChainOpts.  Returns a Chains object."""
+        arr = np.ascontiguousarray(las, dtype=LA_DTYPE)
+        o = default_chain_opts(100 if tspace is None else tspace, **opts)
+        h = ctypes.c_void_p()
+        _check(lib().dh_la_chain(self._h, arr.ctypes.data, len(arr), ctypes.byref(o), ctypes.byref(h)))
+        return Chains(h)
+
     def transpose(self, A, B, las, trace=None, tspace=None, select_best=False):
         """dh_la_transpose: the same alignments with the roles of the sequences exchanged (aread = B read, trace points on
         the B read's grid), from their edit paths.  Returns (las', trace', src_index), LAsort order; src_index[i] is the
@@ -583,6 +614,62 @@ class EditPaths:
                 self._h = None
         except Exception:
             pass
+
+
+class Chains:
+    """Result of Context.chain: numpy views of a library-owned dh_la_chains (alive as long as this object is).  Chain i is
+    the output records off[i]:off[i + 1]; score: per chain; src_index / flags: per output record, the index of the record
+    in the input and the flags it is written with; big_pairs: pairs that took the global-memory tier."""
+
+    def __init__(self, h):
+        L = lib()
+        self._h = h
+        n, nrec = L.dh_la_chains_count(h), L.dh_la_chains_records(h)
+
+        def view(ptr, ctype, count, dtype):
+            if not count:
+                return np.zeros(0, dtype=dtype)
+            buf = (ctype * count).from_address(ptr)
+            buf._owner = self
+            return np.frombuffer(buf, dtype=dtype)
+        self.off = view(L.dh_la_chains_off(h), ctypes.c_int64, n + 1, np.int64)
+        self.score = view(L.dh_la_chains_score(h), ctypes.c_int32, n, np.int32)
+        self.src_index = view(L.dh_la_chains_src_index(h), ctypes.c_int64, nrec, np.int64)
+        self.flags = view(L.dh_la_chains_flags(h), ctypes.c_uint32, nrec, np.uint32)
+        self.big_pairs = int(L.dh_la_chains_big_pairs(h))
+
+    def __len__(self):
+        return len(self.score)
+
+    def to_set(self, las, trace, tspace):
+        """dh_la_chains_to_set: (records, trace) of the chained set in output order; las / trace: what was chained"""
+        arr = np.ascontiguousarray(las, dtype=LA_DTYPE)
+        tr = np.ascontiguousarray(trace, dtype=np.uint16) if trace is not None else None
+        if tr is not None and len(arr) and int((arr["toff"] + arr["tlen"]).max()) > len(tr):
+            raise ValueError("a record's trace lies behind the end of the trace array")
+        h = ctypes.c_void_p()
+        _check(lib().dh_la_chains_to_set(self._h, arr.ctypes.data, len(arr), tr.ctypes.data if tr is not None else None, tspace,
+                                         ctypes.byref(h)))
+        rec, out, _ = _take_la_set(h)
+        return rec, out
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().dh_la_chains_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def default_chain_opts(tspace, **kw):
+    o = ChainOpts()
+    lib().dh_default_chain_opts(ctypes.byref(o), tspace)
+    for k, v in kw.items():
+        if k == "pad_" or not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
 
 
 def _format(fn, *args):

@@ -119,6 +119,12 @@ enum DhSlot : int {
     // batch of verify units
     SLOT_LOC_TEXT, SLOT_LOC_STARTS, SLOT_LOC_PW, SLOT_LOC_PATS, SLOT_LOC_MEMB, SLOT_LOC_TABLE, SLOT_LOC_BITMAP, SLOT_LOC_SHORTS,
     SLOT_LOC_CANDS, SLOT_LOC_COUNTER, SLOT_LOC_UNITS,
+    // chaining (dh_la_chain, dh_chain.cpp): all live for one call.  The nodes, pair offsets and tier lists are the plan;
+    // SLOT_CH_WOFF / SLOT_CH_SLAB are the global tier's array offsets and its slab (rewritten by every launch group);
+    // SLOT_CH_STATE / SLOT_CH_KEY are per node, SLOT_CH_CNT_* per pair (counts, then their exclusive scans), SLOT_CH_SUMS /
+    // SLOT_CH_TOTAL the scans' block sums and 64-bit totals, SLOT_CH_OUT_* the result arrays before they are copied back
+    SLOT_CH_NODES, SLOT_CH_PAIR_OFF, SLOT_CH_LIST, SLOT_CH_WOFF, SLOT_CH_SLAB, SLOT_CH_STATE, SLOT_CH_KEY, SLOT_CH_CNT_REC,
+    SLOT_CH_CNT_CH, SLOT_CH_SUMS, SLOT_CH_TOTAL, SLOT_CH_OUT_OFF, SLOT_CH_OUT_SCORE, SLOT_CH_OUT_SRC, SLOT_CH_OUT_FLAGS,
     DH_SLOT_COUNT
 };
 // The words of SLOT_STATUS (DH_STW_COUNT x int32), one buffer with three users.  All of them run on the context's stream:

@@ -833,6 +833,63 @@ void dh_exact_hits_destroy(dh_exact_hits *h);
 int64_t dh_exact_hits_count(const dh_exact_hits *h);
 const dh_exact_hit *dh_exact_hits_records(const dh_exact_hits *h);
 
+/* ---- chaining of local alignments: chainLocalAlignments / buildAlignmentChains (common/alignments/chaining.d:122-334) with
+ *      its ChainingOptions (:78-118) as a call of its own -- what `dentist chain-local-alignments` writes and what
+ *      `dentist check-results` runs on the alignments of the result against the true contigs (commands/checkResults.d:
+ *      617-624); tools/chain-local-alignments is the drop-in.  Kernels: csrc/dh_chain.hip (one wavefront per pair).
+ *   Input.  Records with DISABLED are dropped (chaining.d:130).  The enabled records must be non-decreasing in (aread,
+ *      bread) (:132-141); otherwise the call returns DH_EINVAL naming the first offending record, found before any launch.
+ *      Both strands of a pair form one group.  START, NEXT and BEST on the input are ignored and cleared: the call is for
+ *      unchained input.  Re-chaining a chained file (the reference carries an alternate flag over) is outside the contract.
+ *   Per pair.  The nodes are ordered by (abpos, bbpos, input index): a topological order of areChainable (:434-451).  Node
+ *      weight is -alignmentScore (:455-461), edge weight is chainScore (:467-475), both in int32 arithmetic.  Relaxation runs
+ *      with u ascending and a strict > decides: a later predecessor of equal distance does not replace an earlier one.  The
+ *      two overlap tests and both thresholds use double, as the reference does: overlap <= max_relative_overlap * minLength
+ *      and (int32_t) max((double) min_score, min_relative_score * best).
+ *   Components and selection.  Components are those of the undirected relation (:182).  Per component the end nodes within
+ *      that component's threshold are taken best first; ties go to the lower position in the node order; a node already on a
+ *      taken chain is no end node.  A chain whose path runs into taken nodes is an alternate chain and consists of its whole
+ *      path (:254-287).  The chains scoring at least the pair's threshold are accepted (:307-318).
+ *   Output.  Each accepted chain is one contiguous run.  Its first record carries COMP | START, plus BEST unless the chain is
+ *      alternate; the other records carry COMP | NEXT (dazzler.d:2046-2082) -- COMP as on the input record, like every flag
+ *      bit that is no chain flag.  Pairs come in input order.  Inside a pair chains ascend by (first.abpos, first.bbpos,
+ *      last.aepos, last.bepos) (base.d:766-777); remaining ties go to the position of the end node in the node order.  The
+ *      reference uses an unstable sort at :241 and :320 and a depth-first topological order; those tie rules are not
+ *      properties of the data, ours are the ones oracle/process.py:chain_pile_las documents.
+ *   Edge cases.  A pair with no accepted chain emits nothing (the reference would index an empty array there, :308-309; that
+ *      cannot happen with min_score = trace spacing and daligner -l500).  n == 0, or everything disabled, returns an empty
+ *      result without a launch.  More than 2^31 - 1 output records (or enabled input records) is DH_EOVERFLOW.
+ *   Argument checks.  max_relative_overlap outside (0, 1), min_relative_score outside [0, 1], min_score <= 0, or a negative
+ *      max_indel / max_chain_gap is DH_EINVAL.
+ *   Tiers by enabled records per pair: 1 (a flat kernel, one lane per pair), 2..64 (registers), 65..1536 (LDS), more (a slab
+ *      of global memory; never the host).  Development knobs (tests): DH_CHAIN_LDS_NODES lowers the LDS tier's limit,
+ *      DH_CHAIN_CHUNK_KB bounds the slab of one launch of the global tier (default 1 GiB; one pair always fits). */
+typedef struct dh_chain_opts {          /* ChainingOptions, chaining.d:78-118; 32 bytes */
+    int32_t max_indel;                  /* --max-indel, 1000  (commandline.d:1982) */
+    int32_t max_chain_gap;              /* --max-chain-gap, 10000 (:1819) */
+    int32_t min_score;                  /* --min-score; default = trace spacing (:2165-2173) */
+    int32_t pad_;
+    double  max_relative_overlap;       /* (0, 1), 0.3 (:2014) */
+    double  min_relative_score;         /* [0, 1], 1.0 (:2153) */
+} dh_chain_opts;
+void dh_default_chain_opts(dh_chain_opts *o, int32_t tspace);
+
+typedef struct dh_la_chains dh_la_chains;
+int dh_la_chain(dh_ctx *ctx, const dh_la *las, int64_t n, const dh_chain_opts *o, dh_la_chains **out);
+int dh_la_set_chain(dh_ctx *ctx, const dh_la_set *set, const dh_chain_opts *o, dh_la_chains **out);
+void dh_la_chains_destroy(dh_la_chains *c);
+int64_t dh_la_chains_count(const dh_la_chains *c);              /* chains */
+int64_t dh_la_chains_records(const dh_la_chains *c);            /* output records, >= chains */
+const int64_t  *dh_la_chains_off(const dh_la_chains *c);        /* count + 1: chain i = output records [off[i], off[i+1]) */
+const int32_t  *dh_la_chains_score(const dh_la_chains *c);      /* per chain: -distance of its end node */
+const int64_t  *dh_la_chains_src_index(const dh_la_chains *c);  /* per output record: index in las */
+const uint32_t *dh_la_chains_flags(const dh_la_chains *c);      /* per output record: the flags it is written with */
+int64_t dh_la_chains_big_pairs(const dh_la_chains *c);          /* pairs that took the global-memory tier (tests) */
+/* host only: the chained set, records and traces gathered in output order (a shared record's trace is copied per occurrence).
+ * trace == NULL: records only (tlen kept, toff 0, no trace values: such a set is not for dh_las_write) */
+int dh_la_chains_to_set(const dh_la_chains *c, const dh_la *las, int64_t n, const uint16_t *trace /* or NULL */,
+                        int32_t tspace, dh_la_set **out);
+
 /* ---- gap-closed assembly writer (host only): the linear-scaffold subset of `dentist output`
  *      (source/dentist/commands/output.d:743-925): header "<id>\tscaffold-<first contig id>", contig
  *      slices lower case, insertions upper case (highlight != 0), unclosed gaps as 'n' runs, lines

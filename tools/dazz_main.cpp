@@ -38,6 +38,11 @@
 //                                    complement) in the records (lines) of <reference>, one TAB-separated line per hit
 //                                    (dh_exact_locate): the reference's external/fm-index.cpp as `dentist check-results`
 //                                    calls it (commands/checkResults.d:511-565, 654-687); leaves <reference>.fm9
+//   chain-local-alignments [--max-indel=<bps>] [--max-chain-gap=<bps>] [--max-relative-overlap=<f>] [--min-relative-score=<f>]
+//             [--min-score=<n>] <ref-db> [<reads-db>] <in:las> <out:las>   the local alignments of every (A, B) pair chained
+//                                    (dh_la_chain: chainLocalAlignments, common/alignments/chaining.d:122-334): every accepted
+//                                    chain as one run of records, alternate chains included -- the command of the same name
+//                                    (commands/chainLocalAlignments.d; options commandline.d:945-951, 1813-2165)
 // DENTIST only sees exit codes, files and stdout of these tools; flags it never emits are rejected.
 #include <algorithm>
 #include <cmath>
@@ -1259,6 +1264,80 @@ static int tool_fm_index(const std::vector<std::string> &args)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- chain-local-alignments
+// Unknown options: the usage text and exit 1.  Everything else that fails: the library's message and exit 2.
+static int tool_chain(const std::vector<std::string> &args)
+{
+    const char *usage = "usage: chain-local-alignments [--max-indel=<bps>] [--max-chain-gap=<bps>] [--max-relative-overlap=<f>] "
+                        "[--min-relative-score=<f>] [--min-score=<n>] <ref-db> [<reads-db>] <in:las> <out:las>";
+    auto fail = [](const std::string &what) {
+        fprintf(stderr, "chain-local-alignments: %s\n", what.c_str());
+        return 2;
+    };
+    std::vector<std::string> pos;
+    std::string v_indel, v_gap, v_ovl, v_rel, v_min;
+    for (const std::string &a : args) {
+        auto value = [&](const char *name, std::string &out) {
+            const size_t len = strlen(name);
+            if (a.compare(0, len, name) != 0 || a.size() <= len) return false;
+            out = a.substr(len);
+            return true;
+        };
+        if (value("--max-indel=", v_indel) || value("--max-chain-gap=", v_gap) || value("--max-relative-overlap=", v_ovl) ||
+            value("--min-relative-score=", v_rel) || value("--min-score=", v_min))
+            continue;
+        if (a.size() > 1 && a[0] == '-') die("unknown or malformed option " + a + "\n" + usage);
+        pos.push_back(a);
+    }
+    if (pos.size() != 3 && pos.size() != 4) die(usage);
+    const std::string &in = pos[pos.size() - 2], &out = pos[pos.size() - 1];
+    dh_la_set *set = nullptr, *chained = nullptr;
+    if (dh_las_read(in.c_str(), &set)) return fail(dh_last_error());
+    dh_chain_opts o;
+    dh_default_chain_opts(&o, dh_la_set_tspace(set));
+    auto number = [&](const std::string &v, bool real, double *d, int32_t *i) {
+        if (v.empty()) return true;
+        char *end = nullptr;
+        if (real)
+            *d = strtod(v.c_str(), &end);
+        else
+            *i = (int32_t)strtol(v.c_str(), &end, 10);
+        return end && *end == 0;
+    };
+    if (!number(v_indel, false, nullptr, &o.max_indel) || !number(v_gap, false, nullptr, &o.max_chain_gap) ||
+        !number(v_min, false, nullptr, &o.min_score) || !number(v_ovl, true, &o.max_relative_overlap, nullptr) ||
+        !number(v_rel, true, &o.min_relative_score, nullptr))
+        return fail("an option's value is not a number");
+    // the DBs only say which read ids exist
+    dh_dazz *da = nullptr, *db = nullptr;
+    if (dh_dazz_open(pos[0].c_str(), &da)) return fail(dh_last_error());
+    if (pos.size() == 4 && dh_dazz_open(pos[1].c_str(), &db)) return fail(dh_last_error());
+    const dh_dazz *dbz = db ? db : da;
+    const int64_t n = dh_la_set_count(set);
+    const dh_la *las = dh_la_set_records(set);
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t a = (int64_t)las[i].aread - dh_dazz_first_id(da), b = (int64_t)las[i].bread - dh_dazz_first_id(dbz);
+        if (a < 0 || a >= dh_dazz_nreads(da) || b < 0 || b >= dh_dazz_nreads(dbz))
+            return fail("record " + std::to_string(i) + " of " + in + ": a read id outside the DB");
+    }
+    dh_ctx *ctx = nullptr;
+    if (dh_ctx_create(0, nullptr, &ctx)) return fail(dh_last_error());
+    dh_la_chains *chains = nullptr;
+    if (dh_la_chain(ctx, las, n, &o, &chains)) return fail(dh_last_error());
+    if (dh_la_chains_to_set(chains, las, n, dh_la_set_trace(set), dh_la_set_tspace(set), &chained)) return fail(dh_last_error());
+    static const uint16_t no_trace = 0;
+    const uint16_t *tr = dh_la_set_trace(chained);
+    if (dh_las_write(out.c_str(), dh_la_set_records(chained), dh_la_set_count(chained), tr ? tr : &no_trace, dh_la_set_tspace(chained)))
+        return fail(dh_last_error());
+    dh_la_chains_destroy(chains);
+    dh_la_set_destroy(chained);
+    dh_la_set_destroy(set);
+    if (db) dh_dazz_close(db);
+    dh_dazz_close(da);
+    dh_ctx_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     g_tool = argv[0];
@@ -1291,6 +1370,7 @@ int main(int argc, char **argv)
     if (g_tool == "DBnw") return tool_dbnw(args);
     if (g_tool == "stretcher") return tool_stretcher(args);
     if (g_tool == "fm-index") return tool_fm_index(args);
+    if (g_tool == "chain-local-alignments") return tool_chain(args);
     die("unknown tool (expected fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv "
         "computeintrinsicqv daccord merge-insertions)");
     return 1;
