@@ -71,6 +71,71 @@ def test_tile_qv_with_more_overlaps_than_fit_the_staging(gpu_ctx):
         assert np.array_equal(got, exp)
 
 
+def qv_range_case(ts=100, full=24):
+    """Fabricated records (consensus_cases.overlap with the trace pairs given) whose tile values spread over 0 .. 200: every
+    tile of 100 columns holds both values around one border between two lanes' groups of four bins (3 / 4, 7 / 8, ...
+    199 / 200) and one overlap with as many diffs as its longer side has bases among some 20 values up to 25, so that the
+    mean stays below the cap of 50 and shows every bin; reads of k * ts and k * ts + 1 bases (a last tile of one column);
+    overlaps that begin or end inside a tile or on a tile boundary, and disabled ones.  `full` overlaps span their read:
+    its first tile is covered by `full` overlaps, its last one by full + 1.  The stage and the oracle read records and
+    trace pairs only, never B bases: the pairs are given as they are (no alignment behind them) and a record's B interval
+    may be longer than the read it names.  Returns (read lengths, records, trace)."""
+    import consensus_cases as cc
+    rng = np.random.default_rng(11)
+    rl = np.array([600, 601, 600, 601, 550], dtype=np.int64)
+
+    # value -> (diffs, B bases) of a full tile, diffs at most the longer side (not every value above 100 can be had)
+    pair_for = {}
+    for b in range(2 * ts, -1, -1):
+        for dd in range(max(ts, b) + 1):
+            pair_for[200 * dd // (ts + b)] = (dd, b)
+    # the values next to every border between two lanes' bins: the highest one that can be had below, the lowest one above
+    borders = [v for k in range(1, 51) for v in (max(x for x in pair_for if x < 4 * k), min(x for x in pair_for if x >= 4 * k))]
+    assert all(lo // 4 + 1 == hi // 4 for lo, hi in zip(borders[0::2], borders[1::2])) and borders[-1] == 200
+    recs, tr, seen = [], [], set()
+    toff = 0
+    for a in range(len(rl)):
+        n = int(rl[a])
+        spans = [(0, n, 0)] * full + [(30, n - 20, 0), (100, 250, 0), (0, n, 1), (200, n, 0), (99, 301, 0)]
+        for i, (ab, ae, off) in enumerate(spans):
+            pairs = []
+            for t in range(ab // ts, (ae - 1) // ts + 1):
+                alen = min((t + 1) * ts, ae) - max(t * ts, ab)
+                if alen == ts and i < 4:           # four border values per tile; 5 reads x 5 tiles x 4 = all 100
+                    v = borders[((5 * a + t) * 4 + i) % len(borders)]
+                    seen.add(v)
+                    pairs.append(pair_for[v])
+                elif i in (5, full + 1):           # as many diffs as the longer side has bases
+                    b = int(rng.integers(0, 2 * alen + 1))
+                    pairs.append((max(alen, b), b))
+                else:
+                    b = int(rng.integers(max(alen - 10, 0), alen + 11))
+                    pairs.append((int(rng.integers(0, min(26, max(alen, b) + 1))), b))
+            nb = sum(p[1] for p in pairs)
+            la, pairs, _ = cc.overlap(np.zeros(n, np.uint8), ab, ae, np.zeros(nb, np.uint8), 0, nb, ts, pairs=pairs)
+            la["aread"], la["bread"], la["toff"], la["flags"] = a, (a + 1 + i) % len(rl), toff, 0x20 if off else 0
+            recs.append(la)
+            tr.append(pairs.reshape(-1))
+            toff += pairs.size
+    assert seen == set(borders)
+    return rl, np.ascontiguousarray(np.concatenate(recs)), np.ascontiguousarray(np.concatenate(tr))
+
+
+def test_tile_qv_over_the_whole_value_range(gpu_ctx):
+    """k_tile_qv on qv_range_case() with cov = 1, m - 1, m, m + 1 for tiles covered by m = 24 and m = 25 overlaps."""
+    ts, full = 100, 24
+    rl, las, trace = qv_range_case(ts, full)
+    reads = sim.SeqDb(np.zeros(int(rl.sum()), dtype=np.uint8), np.concatenate([[0], np.cumsum(rl)]))
+    d = gpu_ctx.db(reads)
+    ref = oz.tile_qv(las, trace, rl.astype(np.int32), ts, 1000)
+    known = ref[ref != 255]
+    assert known.max() == 50 and (known < 50).mean() > 0.8    # most means below the cap: every bin shows
+    for cov in (1, full - 1, full, full + 1, full + 2, 1000):
+        exp = oz.tile_qv(las, trace, rl.astype(np.int32), ts, cov)
+        got = dentist_amd.tile_qv(gpu_ctx, d, las, trace, ts, cov, exp.shape[1])
+        assert np.array_equal(got, exp), cov
+
+
 @pytest.mark.parametrize("seed", [41, 47])
 def test_consensus_of_one_read_matches_the_oracle(gpu_ctx, seed):
     reads = pile_case(seed)
