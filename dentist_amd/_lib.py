@@ -114,6 +114,8 @@ SYMBOLS = [
     "dh_default_chain_opts", "dh_la_chain", "dh_la_set_chain", "dh_la_chains_destroy", "dh_la_chains_count", "dh_la_chains_records",
     "dh_la_chains_off", "dh_la_chains_score", "dh_la_chains_src_index", "dh_la_chains_flags", "dh_la_chains_big_pairs",
     "dh_la_chains_to_set",
+    "dh_la_propagate_mask", "dh_la_set_propagate_mask", "dh_mask_result_destroy", "dh_mask_result_count", "dh_mask_result_ptr",
+    "dh_mask_result_iv", "dh_mask_result_raw", "dh_mask_result_hit", "dh_mask_result_passes",
 ]
 
 _LIB = None
@@ -264,6 +266,18 @@ def lib():
         getattr(L, "dh_la_chains_" + name).argtypes = [vp]
         getattr(L, "dh_la_chains_" + name).restype = vp
     L.dh_la_chains_to_set.argtypes = [vp, vp, i64, vp, i32, ctypes.POINTER(vp)]
+    L.dh_la_propagate_mask.argtypes = [vp, vp, i64, vp, i64, i32, vp, vp, i32, vp, i32, ctypes.POINTER(vp)]
+    L.dh_la_set_propagate_mask.argtypes = [vp, vp, vp, vp, i32, vp, i32, ctypes.POINTER(vp)]
+    L.dh_mask_result_destroy.argtypes = [vp]
+    L.dh_mask_result_destroy.restype = None
+    for name in ("count", "raw", "hit"):
+        getattr(L, "dh_mask_result_" + name).argtypes = [vp]
+        getattr(L, "dh_mask_result_" + name).restype = i64
+    for name in ("ptr", "iv"):
+        getattr(L, "dh_mask_result_" + name).argtypes = [vp]
+        getattr(L, "dh_mask_result_" + name).restype = vp
+    L.dh_mask_result_passes.argtypes = [vp]
+    L.dh_mask_result_passes.restype = i32
     _LIB = L
     return L
 
@@ -550,6 +564,31 @@ class Context:
         _check(lib().dh_la_chain(self._h, arr.ctypes.data, len(arr), ctypes.byref(o), ctypes.byref(h)))
         return Chains(h)
 
+    def propagate_mask(self, las, trace, tspace, mask, ncontigs, read_off):
+        """dh_la_propagate_mask: the contig mask (ptr, iv) carried to the reads on the device (propagateMask.d:136-305); the
+        arguments of the module-level propagate_mask.  Returns a PropagatedMask.  A DeviceTrace as `trace` (map_reads with
+        trace_on_device=True) takes the records, trace values and tspace of its result set (dh_la_set_propagate_mask): the
+        values are used where they are."""
+        mp = np.ascontiguousarray(mask[0], dtype=np.int64)
+        mi = np.ascontiguousarray(np.concatenate([np.asarray(mask[1], dtype=np.int32).reshape(-1), [0, 0]]), dtype=np.int32)
+        ro = np.ascontiguousarray(read_off, dtype=np.int64)
+        if len(mp) != int(ncontigs) + 1 or len(ro) < 1:
+            raise ValueError("mask[0] needs ncontigs + 1 entries, read_off nreads + 1")
+        if len(mp) and 2 * int(mp.max()) > len(mi) - 2:
+            raise ValueError("the mask's ptr lies behind the end of its intervals")
+        h = ctypes.c_void_p()
+        L = lib()
+        if isinstance(trace, DeviceTrace):
+            _check(L.dh_la_set_propagate_mask(self._h, trace._h, mp.ctypes.data, mi.ctypes.data, int(ncontigs), ro.ctypes.data, len(ro) - 1,
+                                              ctypes.byref(h)))
+        else:
+            arr = np.ascontiguousarray(las, dtype=LA_DTYPE)
+            tr = np.ascontiguousarray(trace, dtype=np.uint16)
+            _check(L.dh_la_propagate_mask(self._h, arr.ctypes.data if len(arr) else None, len(arr), tr.ctypes.data if len(tr) else None,
+                                          len(tr), int(tspace), mp.ctypes.data, mi.ctypes.data, int(ncontigs), ro.ctypes.data, len(ro) - 1,
+                                          ctypes.byref(h)))
+        return PropagatedMask(h, len(ro) - 1)
+
     def transpose(self, A, B, las, trace=None, tspace=None, select_best=False):
         """dh_la_transpose: the same alignments with the roles of the sequences exchanged (aread = B read, trace points on
         the B read's grid), from their edit paths.  Returns (las', trace', src_index), LAsort order; src_index[i] is the
@@ -660,6 +699,28 @@ class Chains:
                 self._h = None
         except Exception:
             pass
+
+
+class PropagatedMask:
+    """Result of Context.propagate_mask: ptr int64[nreads + 1] and iv int32[m, 2], laid out as the module-level
+    propagate_mask returns them (copies); raw: non-empty intervals before the union, hit: records with an intersecting mask
+    interval, passes: destination ranges the call took."""
+
+    def __init__(self, h, nreads):
+        L = lib()
+        try:
+            m = int(L.dh_mask_result_count(h))
+            self.ptr = np.zeros(nreads + 1, dtype=np.int64)
+            ctypes.memmove(self.ptr.ctypes.data, L.dh_mask_result_ptr(h), 8 * (nreads + 1))
+            self.iv = np.zeros((m, 2), dtype=np.int32)
+            if m:
+                ctypes.memmove(self.iv.ctypes.data, L.dh_mask_result_iv(h), 8 * m)
+            self.raw, self.hit, self.passes = int(L.dh_mask_result_raw(h)), int(L.dh_mask_result_hit(h)), int(L.dh_mask_result_passes(h))
+        finally:
+            L.dh_mask_result_destroy(h)
+
+    def __len__(self):
+        return len(self.iv)
 
 
 def default_chain_opts(tspace, **kw):

@@ -125,6 +125,14 @@ enum DhSlot : int {
     // SLOT_CH_TOTAL the scans' block sums and 64-bit totals, SLOT_CH_OUT_* the result arrays before they are copied back
     SLOT_CH_NODES, SLOT_CH_PAIR_OFF, SLOT_CH_LIST, SLOT_CH_WOFF, SLOT_CH_SLAB, SLOT_CH_STATE, SLOT_CH_KEY, SLOT_CH_CNT_REC,
     SLOT_CH_CNT_CH, SLOT_CH_SUMS, SLOT_CH_TOTAL, SLOT_CH_OUT_OFF, SLOT_CH_OUT_SCORE, SLOT_CH_OUT_SRC, SLOT_CH_OUT_FLAGS,
+    // mask propagation (dh_la_propagate_mask, dh_pmask.cpp): all live for one call.  The compact records, the mask, the bit
+    // offsets of the destination sequences and (unless the set holds them on the device) the trace values are the input;
+    // SLOT_PM_LO / CNT / OFF / HAS are per record (first interval, count, and the scans that place the raw intervals and
+    // compact the records), SLOT_PM_LIST the records with any, SLOT_PM_RAW the raw list, written once; SLOT_PM_BITMAP,
+    // SLOT_PM_CS / CE (run starts and ends per group of words, then their scans) and SLOT_PM_IV are rewritten by every
+    // destination range; SLOT_PM_PTR collects ptr, SLOT_PM_SUMS / SLOT_PM_TOTAL are the scans' block sums and the counters
+    SLOT_PM_RECS, SLOT_PM_MASK_PTR, SLOT_PM_MASK_IV, SLOT_PM_BOFF, SLOT_PM_TRACE, SLOT_PM_LO, SLOT_PM_CNT, SLOT_PM_OFF, SLOT_PM_HAS,
+    SLOT_PM_LIST, SLOT_PM_RAW, SLOT_PM_BITMAP, SLOT_PM_CS, SLOT_PM_CE, SLOT_PM_IV, SLOT_PM_PTR, SLOT_PM_SUMS, SLOT_PM_TOTAL,
     DH_SLOT_COUNT
 };
 // The words of SLOT_STATUS (DH_STW_COUNT x int32), one buffer with three users.  All of them run on the context's stream:

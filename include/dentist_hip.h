@@ -890,6 +890,43 @@ int64_t dh_la_chains_big_pairs(const dh_la_chains *c);          /* pairs that to
 int dh_la_chains_to_set(const dh_la_chains *c, const dh_la *las, int64_t n, const uint16_t *trace /* or NULL */,
                         int32_t tspace, dh_la_set **out);
 
+/* ---- mask propagation on the device: `dentist propagate-mask` (commands/propagateMask.d:136-305), which the workflow runs
+ *      twice per mask and read block over the full mapping (snakemake/Snakefile:1218-1255); tools/propagate-mask is the
+ *      drop-in.  Kernels: csrc/dh_pmask.hip.  The result is that of dh_propagate_mask above.
+ *   Contract.  For every record and every mask interval of its A sequence that intersects [abpos, aepos): the interval is cut
+ *      to [abpos, aepos) (:214-262); its begin is translated with translateTracePoint(floor), its end with (ceil) (:264-293,
+ *      base.d:185-203); records with DH_FLAG_COMP mirror it to [blen - e, blen - b) (:295-300); empty results are dropped.
+ *      Per destination sequence the result is the union of what is left: sorted, intersecting or touching intervals merged
+ *      (:307-313, util/region.d:776-816).  No flag other than COMP matters; the records may come in any order.
+ *   Input.  trace_len = entries of `trace`.  mask_ptr[ncontigs + 1] / mask_iv as for dh_propagate_mask; read_off[nreads + 1]
+ *      gives the lengths of the destination sequences.  The set form takes records, trace values and tspace from the set; trace
+ *      values that dh_map_reads left on the device (want_sorted & 8) are used where they are and are still there afterwards.
+ *   Refusals, all DH_EINVAL, never a fault; dh_last_error names the lowest offending record index (the contig for the mask).
+ *      Found on the host before anything is launched: aread or bread out of range; abpos < 0 or abpos > aepos; tlen negative,
+ *      odd or not 2 * ((aepos + tspace - 1) / tspace - abpos / tspace); toff + tlen behind trace_len; a mask that is not, per
+ *      contig, sorted with 0 <= begin < end and begin >= the end before it (touching is allowed, an empty interval is not: the
+ *      reference's Region never holds one).  Found by the kernel before anything is painted: a translated position outside
+ *      [0, blen], i.e. a trace whose b-bases run past the read.
+ *   How.  One bit per destination base; sequence r starts at a bit offset that is a multiple of 32 and is followed by at
+ *      least one bit that is never set.  The destination is handled in consecutive ranges of sequences whose bitmap fits
+ *      DH_PMASK_BITMAP_MB (default 4096; one sequence always fits); the raw intervals are computed once.  The result does not
+ *      depend on the knob, and is the same from run to run.  n == 0, an empty mask and nreads == 0 give an all-zero ptr
+ *      without a launch.  Development knob (tests): DH_PMASK_GROUP_RAW bounds the raw intervals of one launch group of
+ *      records (default and most 2^31, so that the 32-bit scans of a group cannot wrap; one record always fits). */
+typedef struct dh_mask_result dh_mask_result;
+int dh_la_propagate_mask(dh_ctx *ctx, const dh_la *las, int64_t n, const uint16_t *trace, int64_t trace_len,
+                         int32_t tspace, const int64_t *mask_ptr, const int32_t *mask_iv, int32_t ncontigs,
+                         const int64_t *read_off, int32_t nreads, dh_mask_result **out);
+int dh_la_set_propagate_mask(dh_ctx *ctx, const dh_la_set *set, const int64_t *mask_ptr, const int32_t *mask_iv,
+                             int32_t ncontigs, const int64_t *read_off, int32_t nreads, dh_mask_result **out);
+void dh_mask_result_destroy(dh_mask_result *m);
+int64_t dh_mask_result_count(const dh_mask_result *m);        /* intervals */
+const int64_t *dh_mask_result_ptr(const dh_mask_result *m);   /* nreads + 1 */
+const int32_t *dh_mask_result_iv(const dh_mask_result *m);    /* (begin, end) pairs on the forward read */
+int64_t dh_mask_result_raw(const dh_mask_result *m);          /* non-empty intervals before the union (tests) */
+int64_t dh_mask_result_hit(const dh_mask_result *m);          /* records with an intersecting mask interval */
+int32_t dh_mask_result_passes(const dh_mask_result *m);       /* destination ranges (tests) */
+
 /* ---- gap-closed assembly writer (host only): the linear-scaffold subset of `dentist output`
  *      (source/dentist/commands/output.d:743-925): header "<id>\tscaffold-<first contig id>", contig
  *      slices lower case, insertions upper case (highlight != 0), unclosed gaps as 'n' runs, lines

@@ -43,6 +43,10 @@
 //                                    (dh_la_chain: chainLocalAlignments, common/alignments/chaining.d:122-334): every accepted
 //                                    chain as one run of records, alternate chains included -- the command of the same name
 //                                    (commands/chainLocalAlignments.d; options commandline.d:945-951, 1813-2165)
+//   propagate-mask -m <mask> [-m <mask>]... <ref-db> [<reads-db>] <db-alignment> <out-mask>   the union of the masks of <ref-db>
+//                                    carried through the alignments to <reads-db> (to <ref-db> itself when it is omitted) and
+//                                    written there as <out-mask> (dh_la_propagate_mask: `dentist propagate-mask`,
+//                                    commands/propagateMask.d:136-305; snakemake/Snakefile:1218-1255)
 // DENTIST only sees exit codes, files and stdout of these tools; flags it never emits are rejected.
 #include <algorithm>
 #include <cmath>
@@ -1338,6 +1342,95 @@ static int tool_chain(const std::vector<std::string> &args)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- propagate-mask
+// Unknown options: the usage text and exit 1.  Everything else that fails: the library's message and exit 2.
+static int tool_propagate_mask(const std::vector<std::string> &args)
+{
+    const char *usage = "usage: propagate-mask -m <mask> [-m <mask>]... [--config=<file>] [-v] [--quiet] [-T<n>] <ref-db> [<reads-db>] "
+                        "<db-alignment> <out-mask>";
+    auto fail = [](const std::string &what) {
+        fprintf(stderr, "propagate-mask: %s\n", what.c_str());
+        return 2;
+    };
+    std::vector<std::string> pos, masks;
+    bool ignored = false;
+    for (size_t i = 0; i < args.size(); i++) {
+        const std::string &a = args[i];
+        if (a == "-m" && i + 1 < args.size())
+            masks.push_back(args[++i]);
+        else if (a.size() > 2 && a.compare(0, 2, "-m") == 0)
+            masks.push_back(a.substr(2));
+        else if (a.size() > 7 && a.compare(0, 7, "--mask=") == 0)
+            masks.push_back(a.substr(7));
+        else if (a == "-v" || a == "--quiet" || (a.size() > 9 && a.compare(0, 9, "--config=") == 0) ||
+                 (a.size() > 2 && a.compare(0, 2, "-T") == 0) || (a.size() > 10 && a.compare(0, 10, "--threads=") == 0))
+            ignored = true;
+        else if (a.size() > 1 && a[0] == '-')
+            die("unknown or malformed option " + a + "\n" + usage);
+        else
+            pos.push_back(a);
+    }
+    if (masks.empty() || (pos.size() != 3 && pos.size() != 4)) die(usage);
+    if (ignored) fprintf(stderr, "propagate-mask: --config, -v, --quiet, -T and --threads have no effect here\n");
+    const std::string &in = pos[pos.size() - 2], &out_name = pos[pos.size() - 1], &dest_path = pos.size() == 4 ? pos[1] : pos[0];
+    dh_dazz *da = nullptr, *db = nullptr;
+    if (dh_dazz_open(pos[0].c_str(), &da)) return fail(dh_last_error());
+    if (pos.size() == 4 && dh_dazz_open(pos[1].c_str(), &db)) return fail(dh_last_error());
+    const dh_dazz *dest = db ? db : da;
+    const int32_t ncontigs = dh_dazz_nreads(da), nreads = dh_dazz_nreads(dest);
+    // readMasks (:136-142): the union of the input masks, per contig sorted with intersecting or touching intervals merged
+    std::vector<std::vector<std::pair<int32_t, int32_t>>> per((size_t)ncontigs);
+    for (const std::string &m : masks) {
+        std::vector<int64_t> ptr((size_t)ncontigs + 1);
+        const int64_t cnt = dh_dazz_read_mask(da, pos[0].c_str(), m.c_str(), ptr.data(), nullptr, 0);
+        if (cnt < 0) return fail("mask " + m + ": " + dh_last_error());
+        std::vector<int32_t> iv((size_t)(2 * cnt) + 2);
+        if (dh_dazz_read_mask(da, pos[0].c_str(), m.c_str(), ptr.data(), iv.data(), cnt) < 0) return fail("mask " + m + ": " + dh_last_error());
+        for (int32_t c = 0; c < ncontigs; c++)
+            for (int64_t j = ptr[(size_t)c]; j < ptr[(size_t)c + 1]; j++)
+                if (iv[(size_t)(2 * j + 1)] > iv[(size_t)(2 * j)]) per[(size_t)c].push_back({iv[(size_t)(2 * j)], iv[(size_t)(2 * j + 1)]});
+    }
+    std::vector<int64_t> mask_ptr{0};
+    std::vector<int32_t> mask_iv;
+    for (auto &v : per) {
+        std::sort(v.begin(), v.end());
+        size_t first = mask_iv.size();
+        for (const auto &x : v) {
+            if (mask_iv.size() > first && x.first <= mask_iv.back())
+                mask_iv.back() = std::max(mask_iv.back(), x.second);
+            else {
+                mask_iv.push_back(x.first);
+                mask_iv.push_back(x.second);
+            }
+        }
+        mask_ptr.push_back((int64_t)mask_iv.size() / 2);
+    }
+    mask_iv.push_back(0);  // (never an empty array)
+    dh_la_set *set = nullptr;
+    if (dh_las_read(in.c_str(), &set)) return fail(dh_last_error());
+    const int64_t n = dh_la_set_count(set);
+    std::vector<dh_la> las(dh_la_set_records(set), dh_la_set_records(set) + n);
+    for (dh_la &l : las) {  // ids of the opened views
+        l.aread -= dh_dazz_first_id(da);
+        l.bread -= dh_dazz_first_id(dest);
+    }
+    dh_ctx *ctx = nullptr;
+    if (dh_ctx_create(0, nullptr, &ctx)) return fail(dh_last_error());
+    dh_mask_result *res = nullptr;
+    if (dh_la_propagate_mask(ctx, las.data(), n, dh_la_set_trace(set), dh_la_set_trace_len(set), dh_la_set_tspace(set), mask_ptr.data(),
+                             mask_iv.data(), ncontigs, dh_dazz_offsets(dest), nreads, &res))
+        return fail(dh_last_error());
+    static const int32_t no_iv[2] = {0, 0};
+    const int32_t *iv = dh_mask_result_count(res) > 0 ? dh_mask_result_iv(res) : no_iv;
+    if (dh_dazz_write_mask(dest_path.c_str(), out_name.c_str(), nreads, dh_mask_result_ptr(res), iv)) return fail(dh_last_error());
+    dh_mask_result_destroy(res);
+    dh_la_set_destroy(set);
+    if (db) dh_dazz_close(db);
+    dh_dazz_close(da);
+    dh_ctx_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     g_tool = argv[0];
@@ -1371,6 +1464,7 @@ int main(int argc, char **argv)
     if (g_tool == "stretcher") return tool_stretcher(args);
     if (g_tool == "fm-index") return tool_fm_index(args);
     if (g_tool == "chain-local-alignments") return tool_chain(args);
+    if (g_tool == "propagate-mask") return tool_propagate_mask(args);
     die("unknown tool (expected fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv "
         "computeintrinsicqv daccord merge-insertions)");
     return 1;
