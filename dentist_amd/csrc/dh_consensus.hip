@@ -79,7 +79,7 @@ k_gather_parts(const uint8_t *__restrict__ src0, const int64_t *__restrict__ off
 // ------------------------------------------------------------------------------------ K6b
 // The alignment funnel of computeQVs (processPileUps/package.d:474-516) on the records the pile-up all-vs-all left on
 // the device -- averageErrorRate <= maxAlignmentError, chainLocalAlignments per (A, B) pair (chaining.d:122-334, the
-// arithmetic of dh_process.cpp:chain_pair), isValidPileUpAlignment (dazzler.d:4126-4141) -- so that 3.5 M records
+// arithmetic of dh_tracepoint.cpp:chain_pair), isValidPileUpAlignment (dazzler.d:4126-4141) -- so that 3.5 M records
 // (configs[2]) neither travel to the host nor back for the tile QVs.  One wavefront per A read; its records are one
 // range of the compacted array (item_off: exclusive prefix sums over the items (read, strand)), the records of a pair
 // in ascending index order are what the host sees after its stable merge by B read.  Flags are updated in place:

@@ -566,3 +566,76 @@ int dh_build_index(dh_db *A, int32_t k, int32_t sepv, int32_t kmer_mod, bool lig
     A->has_ix = true;
     return DH_OK;
 }
+
+// ------------------------------------------------------------------------------------ DBs the library makes for itself
+
+extern "C" void dhk_gather_slices(hipStream_t st, const uint8_t *src, const int64_t *src_off, const int32_t *sidx,
+                                  const int32_t *sbeg, const int64_t *dst_off, int32_t n, int32_t max_len,
+                                  uint8_t *dst);
+
+int dh_db_adopt(dh_ctx *ctx, uint8_t *d_alloc, uint8_t *d_bases, const std::vector<int64_t> &off,
+                const std::vector<int32_t> &group, dh_db **out)
+{
+    dh_db *db = new dh_db();
+    db->ctx = ctx;
+    db->n = (int32_t)off.size() - 1;
+    db->h_off = off;
+    db->total = off.back();
+    db->d_bases = d_bases;
+    db->d_bases_alloc = d_alloc;
+    for (int32_t i = 0; i < db->n; i++)
+        db->max_len = std::max<int32_t>(db->max_len, (int32_t)(off[(size_t)i + 1] - off[(size_t)i]));
+    HIPCHK(dh_dev_alloc(&db->d_off, sizeof(int64_t) * off.size()));
+    HIPCHK(hipMemcpyAsync(db->d_off, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice,
+                          ctx->stream));
+    if (!group.empty()) {
+        db->h_group = group;
+        for (int32_t g : group) db->ngroups = std::max(db->ngroups, g + 1);
+        HIPCHK(dh_dev_alloc(&db->d_group, sizeof(int32_t) * group.size()));
+        HIPCHK(hipMemcpyAsync(db->d_group, group.data(), sizeof(int32_t) * group.size(),
+                              hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *out = db;
+    return DH_OK;
+}
+
+int dh_db_from_slices(dh_ctx *ctx, const dh_db *src, const std::vector<int32_t> &sidx,
+                      const std::vector<int32_t> &sbeg, const std::vector<int32_t> &slen,
+                      const std::vector<int32_t> &group, dh_db **out, bool inherit_mask)
+{
+    const int32_t n = (int32_t)sidx.size();
+    std::vector<int64_t> off((size_t)n + 1, 0);
+    int32_t max_len = 0;
+    for (int32_t i = 0; i < n; i++) {
+        off[(size_t)i + 1] = off[(size_t)i] + slen[(size_t)i];
+        max_len = std::max(max_len, slen[(size_t)i]);
+    }
+    uint8_t *d_alloc = nullptr, *d_bases = nullptr;
+    if (int rc = dh_alloc_bases(ctx->stream, off.back(), &d_alloc, &d_bases)) return rc;
+    if (int rc = dh_db_adopt(ctx, d_alloc, d_bases, off, group, out)) {
+        dh_dev_free(d_alloc);
+        return rc;
+    }
+    if (n > 0) {
+        DevBuf<int32_t> d_sidx, d_sbeg;
+        HIPCHK(d_sidx.alloc((size_t)n));
+        HIPCHK(d_sbeg.alloc((size_t)n));
+        HIPCHK(hipMemcpyAsync(d_sidx.p, sidx.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice,
+                              ctx->stream));
+        HIPCHK(hipMemcpyAsync(d_sbeg.p, sbeg.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice,
+                              ctx->stream));
+        dhk_gather_slices(ctx->stream, src->d_bases, src->d_off, d_sidx.p, d_sbeg.p, (*out)->d_off, n,
+                          max_len, d_bases);
+        if (inherit_mask && src->d_mask_bits) {  // slices keep the soft mask of their source (the flank DB's -mrep)
+            uint8_t *layer;
+            if (int rc = dh_ensure_mask_layer(*out, 0, &layer)) return rc;
+            dhk_mask_slices(ctx->stream, (const uint32_t *)src->d_mask_bits, src->d_off, d_sidx.p, d_sbeg.p, (*out)->d_off, n,
+                            max_len, (uint32_t *)layer);
+            if (int rc = dh_mask_recompose(*out)) return rc;
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    return DH_OK;
+}

@@ -100,7 +100,7 @@ enum DhSlot : int {
     SLOT_MJ_SEGTAB, SLOT_MJ_CTR,
     // the per-group table join (seed_chunk, dh_align.cpp): the units, hit segments and hits of one chunk, read by its seeds
     SLOT_TJ_UNITS, SLOT_TJ_SEGTAB, SLOT_TJ_HITS, SLOT_TJ_CTR,
-    // the process rounds (the vote and emit pass of a consensus round, dh_process.cpp): live for one round
+    // the process rounds (the vote and emit pass of a consensus round, dh_rounds.cpp): live for one round
     SLOT_PR_VOFF, SLOT_PR_VOTES, SLOT_PR_OUT, SLOT_PR_STATUS, SLOT_PR_STAGE, SLOT_PR_SEGS, SLOT_PR_DECISIONS, SLOT_PR_CDIFF,
     // comm (dh_comm.cpp: the staging buffers of a collective): live for one collective; several requests (one per kind)
     SLOT_COMM_SEND, SLOT_COMM_RECV,
@@ -339,7 +339,7 @@ void dh_select_best_range(dh_la *la, size_t nla, int32_t near_ppm);
 // LAsort order of a B-major list of records over `na` A reads, in O(n)
 void dh_lasort(dh_la_set *res, int32_t na);
 
-// result of the process stage (dh_process.cpp; dh_comm.cpp assembles the gathered result of all ranks)
+// result of the process stage (made by dh_process.cpp, spliced by dh_batch.cpp, read by dh_insertions.cpp; dh_comm.cpp assembles the gathered result of all ranks)
 struct dh_insertions {
     std::vector<dh_insertion> rec;
     std::vector<uint8_t> bases;
@@ -379,6 +379,7 @@ struct dh_edit_paths {
     int64_t general_tiles = 0;
 };
 
+// dh_pileups.cpp: LA indices shifted by a constant; pile-ups of several parts concatenated gap by gap
 void dh_pileups_shift(dh_pileups *p, int32_t by);
 int dh_pileups_concat(dh_pileups *const *parts, int32_t nparts, dh_pileups **out);
 
@@ -389,7 +390,7 @@ struct DevBuf {
     hipError_t alloc(size_t n) { return dh_dev_alloc(&p, sizeof(T) * std::max<size_t>(n, 1)); }
 };
 
-// build a DB whose bases are slices [beg, beg+len) of sequences of `src` (device-to-device)
+// dh_db.cpp: build a DB whose bases are slices [beg, beg+len) of sequences of `src` (device-to-device)
 int dh_db_from_slices(dh_ctx *ctx, const dh_db *src, const std::vector<int32_t> &sidx,
                       const std::vector<int32_t> &sbeg, const std::vector<int32_t> &slen,
                       const std::vector<int32_t> &group, dh_db **out, bool inherit_mask = false);

@@ -77,7 +77,7 @@ PM_HD void plan_lane(const Rec &r, const int64_t *mask_ptr, const int32_t *mask_
     *cnt_out = (uint32_t)(lo - first);
 }
 
-// ---- translate.  tracePointsUpTo!"contigA" (base.d:205-244) as dh_process.cpp restates it: the index of the trace point a
+// ---- translate.  tracePointsUpTo!"contigA" (base.d:205-244) as dh_tracepoint.cpp restates it: the index of the trace point a
 // position of A is assigned to, mode 0 = floor, 1 = ceil; clamped to [0, ntp]
 PM_HD int32_t tp_index(const Rec &r, int32_t ts, int32_t apos, int32_t mode)
 {

@@ -1,5 +1,5 @@
 """Brute-force restatement of the contract of dh_la_chain (include/dentist_hip.h, "chaining of local alignments"), written
-from that text alone: no code is shared with chain_pair of dh_process.cpp, with dh_chain.h or with the oracle.  Plain Python
+from that text alone: no code is shared with chain_pair of dh_tracepoint.cpp, with dh_chain.h or with the oracle.  Plain Python
 integers and floats (a Python float is the C double).
 
 chain(las, **opts) returns the chains in output order, each as (record indices, flags, score); arrays() flattens them into

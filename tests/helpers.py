@@ -346,7 +346,7 @@ def assert_same_las_of_reads(got, exp, ids):
 
 # ---------------------------------------------------------------- pile-ups of a full-size batch
 def process_part_cuts(counts, nparts=3):
-    """First pile-up of every concurrent part of dh_process_pileups (dh_process.cpp: contiguous runs of the batch with
+    """First pile-up of every concurrent part of dh_process_pileups (plan_part_cuts of dh_batch.cpp: contiguous runs of the batch with
     equal shares of the sum of entries^2, none empty; fewer than 64 pile-ups run in one piece).  Returns [0, cut 1, ..., n]."""
     n = len(counts)
     if n < 64:
