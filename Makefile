@@ -6,7 +6,7 @@ CSRC := dentist_amd/csrc
 LIB := dentist_amd/libdentist_hip.so
 SIM := dentist_amd/sim/libdh_sim.so
 
-DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index chain-local-alignments propagate-mask
+DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index chain-local-alignments propagate-mask validate-regions
 TOOLS := tools/daligner tools/damapper tools/datander tools/dazz_tools $(addprefix tools/,$(DAZZ_TOOLS))
 
 all: $(LIB) $(SIM) oracle $(TOOLS)
@@ -112,3 +112,13 @@ tests/native/libpmask_host.so: tests/native/pmask_host.cpp dentist_amd/csrc/dh_p
 # after a change to dh_pmask.h -- the edge words of the bitmap and the last chunk of a trace are where this code would overrun
 tests/native/pmask_host_san: tests/native/pmask_host_main.cpp tests/native/pmask_host.cpp dentist_amd/csrc/dh_pmask.h include/dentist_hip.h
 	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/pmask_host_main.cpp tests/native/pmask_host.cpp
+
+# the lane code and the host plan of the region validation (dentist_amd/csrc/dh_vreg.h) compiled for the CPU: test infrastructure
+tests/native/libvreg_host.so: tests/native/vreg_host.cpp dentist_amd/csrc/dh_vreg.h include/dentist_hip.h
+	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -o $@ $<
+
+# the same harness and a stand-alone main under the host sanitizers (a program of its own: nothing is preloaded); run it once
+# after a change to dh_vreg.h -- the last entry of a difference array and the ends of the interval lists are where this code
+# would overrun
+tests/native/vreg_host_san: tests/native/vreg_host_main.cpp tests/native/vreg_host.cpp dentist_amd/csrc/dh_vreg.h include/dentist_hip.h
+	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/vreg_host_main.cpp tests/native/vreg_host.cpp

@@ -116,6 +116,10 @@ SYMBOLS = [
     "dh_la_chains_to_set",
     "dh_la_propagate_mask", "dh_la_set_propagate_mask", "dh_mask_result_destroy", "dh_mask_result_count", "dh_mask_result_ptr",
     "dh_mask_result_iv", "dh_mask_result_raw", "dh_mask_result_hit", "dh_mask_result_passes",
+    "dh_la_validate_regions", "dh_la_set_validate_regions", "dh_region_result_destroy", "dh_region_result_count",
+    "dh_region_result_reports", "dh_region_result_weak_count", "dh_region_result_weak", "dh_region_result_span_off",
+    "dh_region_result_span_ids", "dh_region_result_mask_ptr", "dh_region_result_mask_iv", "dh_region_result_mask_count",
+    "dh_region_result_pairs", "dh_region_result_big_regions", "dh_region_result_groups",
 ]
 
 _LIB = None
@@ -278,6 +282,18 @@ def lib():
         getattr(L, "dh_mask_result_" + name).restype = vp
     L.dh_mask_result_passes.argtypes = [vp]
     L.dh_mask_result_passes.restype = i32
+    L.dh_la_validate_regions.argtypes = [vp, vp, i64, vp, i32, vp, i32, i32, i32, i32, i32, ctypes.POINTER(vp)]
+    L.dh_la_set_validate_regions.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, ctypes.POINTER(vp)]
+    L.dh_region_result_destroy.argtypes = [vp]
+    L.dh_region_result_destroy.restype = None
+    L.dh_region_result_count.argtypes = [vp]
+    L.dh_region_result_count.restype = i32
+    for name in ("weak_count", "mask_count", "pairs", "big_regions", "groups"):
+        getattr(L, "dh_region_result_" + name).argtypes = [vp]
+        getattr(L, "dh_region_result_" + name).restype = i64
+    for name in ("reports", "weak", "span_off", "span_ids", "mask_ptr", "mask_iv"):
+        getattr(L, "dh_region_result_" + name).argtypes = [vp]
+        getattr(L, "dh_region_result_" + name).restype = vp
     _LIB = L
     return L
 
@@ -589,6 +605,27 @@ class Context:
                                           ctypes.byref(h)))
         return PropagatedMask(h, len(ro) - 1)
 
+    def validate_regions(self, las, contig_off, regions, min_coverage_reads, min_spanning_reads=3, region_context=1000,
+                         weak_coverage_window=500):
+        """dh_la_validate_regions: `dentist validate-regions` (validateRegions.d:141-512) on the device; the arguments of the
+        module-level validate_regions.  Returns a ValidatedRegions.  `las` may be a raw handle of align_db_block(..., raw=True)
+        (dh_la_set_validate_regions): the records of the set are taken, the handle stays the caller's."""
+        co = np.ascontiguousarray(contig_off, dtype=np.int64)
+        if len(co) < 1:
+            raise ValueError("contig_off needs ncontigs + 1 entries")
+        rg = np.zeros(len(regions), dtype=REGION_DTYPE)
+        r = np.asarray(regions, dtype=np.int32).reshape(-1, 3)
+        rg["contig"], rg["begin"], rg["end"] = r[:, 0], r[:, 1], r[:, 2]
+        h = ctypes.c_void_p()
+        tail = (co.ctypes.data, len(co) - 1, rg.ctypes.data if len(rg) else None, len(rg), int(region_context), int(weak_coverage_window),
+                int(min_coverage_reads), int(min_spanning_reads), ctypes.byref(h))
+        if isinstance(las, ctypes.c_void_p):
+            _check(lib().dh_la_set_validate_regions(self._h, las, *tail))
+        else:
+            arr = np.ascontiguousarray(las, dtype=LA_DTYPE)
+            _check(lib().dh_la_validate_regions(self._h, arr.ctypes.data if len(arr) else None, len(arr), *tail))
+        return ValidatedRegions(h, len(co) - 1)
+
     def transpose(self, A, B, las, trace=None, tspace=None, select_best=False):
         """dh_la_transpose: the same alignments with the roles of the sequences exchanged (aread = B read, trace points on
         the B read's grid), from their edit paths.  Returns (las', trace', src_index), LAsort order; src_index[i] is the
@@ -721,6 +758,38 @@ class PropagatedMask:
 
     def __len__(self):
         return len(self.iv)
+
+
+class ValidatedRegions:
+    """Result of Context.validate_regions (copies): reports REGION_REPORT_DTYPE[nregions] and weak int32[m, 3] as the
+    module-level validate_regions returns them; span_off int64[nregions + 1] and span_ids int32: the bread of the records that
+    span a region, in ascending record index; mask = (ptr int64[ncontigs + 1], iv int32[k, 2]): the weak intervals of all
+    regions merged per contig; pairs: (record, region) pairs that intersect, big_regions: regions that took the global-memory
+    tier, groups: launch groups."""
+
+    def __init__(self, h, ncontigs):
+        L = lib()
+
+        def copy(ptr, shape, dtype):
+            a = np.zeros(shape, dtype=dtype)
+            if a.nbytes:
+                ctypes.memmove(a.ctypes.data, ptr, a.nbytes)
+            return a
+        try:
+            n = int(L.dh_region_result_count(h))
+            self.reports = copy(L.dh_region_result_reports(h), n, REGION_REPORT_DTYPE)
+            self.weak = copy(L.dh_region_result_weak(h), (int(L.dh_region_result_weak_count(h)), 3), np.int32)
+            self.span_off = copy(L.dh_region_result_span_off(h), n + 1, np.int64)
+            self.span_ids = copy(L.dh_region_result_span_ids(h), int(self.span_off[n]), np.int32)
+            self.mask = (copy(L.dh_region_result_mask_ptr(h), ncontigs + 1, np.int64),
+                         copy(L.dh_region_result_mask_iv(h), (int(L.dh_region_result_mask_count(h)), 2), np.int32))
+            self.pairs, self.big_regions, self.groups = (int(L.dh_region_result_pairs(h)), int(L.dh_region_result_big_regions(h)),
+                                                         int(L.dh_region_result_groups(h)))
+        finally:
+            L.dh_region_result_destroy(h)
+
+    def __len__(self):
+        return len(self.reports)
 
 
 def default_chain_opts(tspace, **kw):

@@ -133,6 +133,12 @@ enum DhSlot : int {
     // destination range; SLOT_PM_PTR collects ptr, SLOT_PM_SUMS / SLOT_PM_TOTAL are the scans' block sums and the counters
     SLOT_PM_RECS, SLOT_PM_MASK_PTR, SLOT_PM_MASK_IV, SLOT_PM_BOFF, SLOT_PM_TRACE, SLOT_PM_LO, SLOT_PM_CNT, SLOT_PM_OFF, SLOT_PM_HAS,
     SLOT_PM_LIST, SLOT_PM_RAW, SLOT_PM_BITMAP, SLOT_PM_CS, SLOT_PM_CE, SLOT_PM_IV, SLOT_PM_PTR, SLOT_PM_SUMS, SLOT_PM_TOTAL,
+    // region validation (dh_la_validate_regions, dh_vreg.cpp): all live for one call.  The compact records, the regions in plan
+    // order and their per-contig offsets are the input, SLOT_VR_CNT the three counters per region; the others are rewritten by
+    // every launch group: the segment starts and claimed slots of its regions (AT, CUR), its jobs, pair list, spanning records
+    // (indices, then bread in order), slab, interval counts and intervals
+    SLOT_VR_RECS, SLOT_VR_REGS, SLOT_VR_RPTR, SLOT_VR_CNT, SLOT_VR_AT, SLOT_VR_CUR, SLOT_VR_JOBS, SLOT_VR_PAIRS, SLOT_VR_SPAN_IDX,
+    SLOT_VR_SPAN_OUT, SLOT_VR_SLAB, SLOT_VR_RCNT, SLOT_VR_IV,
     DH_SLOT_COUNT
 };
 // The words of SLOT_STATUS (DH_STW_COUNT x int32), one buffer with three users.  All of them run on the context's stream:

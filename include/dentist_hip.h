@@ -927,6 +927,56 @@ int64_t dh_mask_result_raw(const dh_mask_result *m);          /* non-empty inter
 int64_t dh_mask_result_hit(const dh_mask_result *m);          /* records with an intersecting mask interval */
 int32_t dh_mask_result_passes(const dh_mask_result *m);       /* destination ranges (tests) */
 
+/* ---- region validation on the device: `dentist validate-regions` (commands/validateRegions.d:141-512), which the workflow
+ *      runs per validation block over the mapping of all reads onto the gap-closed assembly (snakemake/Snakefile:1425-1466);
+ *      tools/validate-regions is the drop-in.  Kernels: csrc/dh_vreg.hip.  Reports and weak triples are those of
+ *      dh_validate_regions above.
+ *   Contract.  For region r = (contig, begin, end): cb = begin > region_context ? begin - region_context : 0 and
+ *      ce = min(end + region_context, contig length) (:178-190).  A record of the contig spans the region iff abpos < cb and
+ *      ce < aepos (:409-420); num_spanning_reads is their number and their bread values are the region's spanning ids, in
+ *      ascending record index.  wlen = min(weak_coverage_window, ce - cb); the windows [w, w + wlen), w = cb .. ce - wlen, are
+ *      considered iff wlen > 0 and a record of the contig has abpos < ce && cb < aepos (:458); a record spans a window iff
+ *      abpos <= w && w + wlen <= aepos; a window spanned by fewer than min_coverage_reads records is weak.  Weak windows are
+ *      intervals, one fused with the one before it when its begin is <= that one's end (:485-498); weak_bp = the sum of the
+ *      interval lengths; is_valid = num_spanning_reads >= min_spanning_reads && weak_bp == 0.  The mask is, per contig, the union
+ *      of the weak intervals of all regions: sorted, intersecting or touching intervals merged (util/region.d:776-816).
+ *      Regions may come in any order, overlap, nest and repeat.
+ *   Input.  las: sorted at least by aread; contig_off[ncontigs + 1] gives the contig lengths.  The set form takes the records
+ *      of the set.
+ *   Refusals, all DH_EINVAL, found on the host before anything is launched, never a fault; dh_last_error names the lowest
+ *      offending index: the bad arguments of dh_validate_regions; a contig longer than 2^31 - 1; a record with aread outside
+ *      [0, ncontigs), with aread below that of the record before it ("reads-alignment must be sorted at least by a-read ID"),
+ *      with abpos < 0, abpos > aepos or aepos behind the end of its contig; a region with contig outside [0, ncontigs),
+ *      begin < 0 or end < begin.
+ *   How.  One lane per record finds the regions of its contig that it touches (the regions sorted by cb, two binary searches)
+ *      and counts; the regions are then handled in launch groups whose pair lists, spanning lists and slab parts fit
+ *      DH_VREG_SLAB_MB (default 1024; one region always fits), one workgroup per region.  The result does not depend on the
+ *      knob and is the same from run to run.  n == 0 or nregions == 0 give the answer of dh_validate_regions without a launch.
+ *      Development knob (tests): DH_VREG_LDS_WINDOWS, the most entries (window starts + 1) of a region whose difference array
+ *      stays in LDS (default 8192, at most 16000). */
+typedef struct dh_region_result dh_region_result;
+int dh_la_validate_regions(dh_ctx *ctx, const dh_la *las, int64_t n, const int64_t *contig_off, int32_t ncontigs,
+                           const dh_region *regions, int32_t nregions, int32_t region_context,
+                           int32_t weak_coverage_window, int32_t min_coverage_reads, int32_t min_spanning_reads,
+                           dh_region_result **out);
+int dh_la_set_validate_regions(dh_ctx *ctx, const dh_la_set *set, const int64_t *contig_off, int32_t ncontigs,
+                               const dh_region *regions, int32_t nregions, int32_t region_context,
+                               int32_t weak_coverage_window, int32_t min_coverage_reads, int32_t min_spanning_reads,
+                               dh_region_result **out);
+void dh_region_result_destroy(dh_region_result *r);
+int32_t dh_region_result_count(const dh_region_result *r);                    /* regions */
+const dh_region_report *dh_region_result_reports(const dh_region_result *r);  /* in input order */
+int64_t dh_region_result_weak_count(const dh_region_result *r);               /* weak intervals of all regions */
+const int32_t *dh_region_result_weak(const dh_region_result *r);              /* (contig, begin, end) triples in region order */
+const int64_t *dh_region_result_span_off(const dh_region_result *r);          /* nregions + 1 */
+const int32_t *dh_region_result_span_ids(const dh_region_result *r);          /* bread of the spanning records */
+const int64_t *dh_region_result_mask_ptr(const dh_region_result *r);          /* ncontigs + 1 */
+const int32_t *dh_region_result_mask_iv(const dh_region_result *r);           /* (begin, end) pairs of the merged mask */
+int64_t dh_region_result_mask_count(const dh_region_result *r);               /* intervals of the merged mask */
+int64_t dh_region_result_pairs(const dh_region_result *r);        /* (record, region) pairs with abpos < ce && cb < aepos (tests) */
+int64_t dh_region_result_big_regions(const dh_region_result *r);  /* regions whose difference array took the slab (tests) */
+int64_t dh_region_result_groups(const dh_region_result *r);       /* launch groups (tests) */
+
 /* ---- gap-closed assembly writer (host only): the linear-scaffold subset of `dentist output`
  *      (source/dentist/commands/output.d:743-925): header "<id>\tscaffold-<first contig id>", contig
  *      slices lower case, insertions upper case (highlight != 0), unclosed gaps as 'n' runs, lines

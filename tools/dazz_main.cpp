@@ -47,6 +47,12 @@
 //                                    carried through the alignments to <reads-db> (to <ref-db> itself when it is omitted) and
 //                                    written there as <out-mask> (dh_la_propagate_mask: `dentist propagate-mask`,
 //                                    commands/propagateMask.d:136-305; snakemake/Snakefile:1218-1255)
+//   validate-regions [--min-coverage-reads=<n> | --read-coverage=<f> --ploidy=<n>] [--min-spanning-reads=<n>]
+//                    [--region-context=<bps>] [--weak-coverage-window=<bps>] [--weak-coverage-mask=<mask>] [--report-all]
+//                    <ref-db> <reads-db> <in.las> <regions-mask>
+//                                    one JSON line per invalid region (per region with --report-all) of the mask <regions-mask>
+//                                    of <ref-db>, the weak-coverage mask written on request (dh_la_validate_regions: `dentist
+//                                    validate-regions`, commands/validateRegions.d:141-512; snakemake/Snakefile:1425-1466)
 // DENTIST only sees exit codes, files and stdout of these tools; flags it never emits are rejected.
 #include <algorithm>
 #include <cmath>
@@ -1431,6 +1437,120 @@ static int tool_propagate_mask(const std::vector<std::string> &args)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- validate-regions
+// Unknown options: the usage text and exit 1.  Everything else that fails: the library's message and exit 2.
+static int tool_validate_regions(const std::vector<std::string> &args)
+{
+    const char *usage = "usage: validate-regions [--min-coverage-reads=<n> | --read-coverage=<f> --ploidy=<n>] [--min-spanning-reads=<n>] "
+                        "[--region-context=<bps>] [--weak-coverage-window=<bps>] [--weak-coverage-mask=<mask>] [--report-all] "
+                        "[--config=<file>] [-v] [--quiet] [-T<n>] <ref-db> <reads-db> <in.las> <regions-mask>";
+    auto fail = [](const std::string &what) {
+        fprintf(stderr, "validate-regions: %s\n", what.c_str());
+        return 2;
+    };
+    std::vector<std::string> pos;
+    std::string v_min_cov, v_cov, v_ploidy, v_span, v_context, v_window, out_mask;
+    bool ignored = false, report_all = false;
+    auto value = [](const std::string &a, const char *key, std::string *out) {
+        const size_t k = strlen(key);
+        if (a.size() <= k || a.compare(0, k, key) != 0) return false;
+        *out = a.substr(k);
+        return true;
+    };
+    for (const std::string &a : args) {
+        if (value(a, "--min-coverage-reads=", &v_min_cov) || value(a, "--read-coverage=", &v_cov) || value(a, "--ploidy=", &v_ploidy) ||
+            value(a, "--min-spanning-reads=", &v_span) || value(a, "--region-context=", &v_context) ||
+            value(a, "--weak-coverage-window=", &v_window) || value(a, "--weak-coverage-mask=", &out_mask))
+            continue;
+        if (a == "--report-all")
+            report_all = true;
+        else if (a == "-v" || a == "--quiet" || (a.size() > 9 && a.compare(0, 9, "--config=") == 0) ||
+                 (a.size() > 2 && a.compare(0, 2, "-T") == 0) || (a.size() > 10 && a.compare(0, 10, "--threads=") == 0))
+            ignored = true;
+        else if (a.size() > 1 && a[0] == '-')
+            die("unknown or malformed option " + a + "\n" + usage);
+        else
+            pos.push_back(a);
+    }
+    if (pos.size() != 4) die(usage);
+    if (ignored) fprintf(stderr, "validate-regions: --config, -v, --quiet, -T and --threads have no effect here\n");
+    // the defaults of commandline.d:2187, 2411, 2497; the coverage options of :2060-2088
+    int32_t min_cov = 0, min_span = 3, context = 1000, window = 500, ploidy = 0;
+    double read_cov = 0;
+    auto number = [](const std::string &v, bool real, double *d, int32_t *i) {
+        if (v.empty()) return true;
+        char *end = nullptr;
+        if (real)
+            *d = strtod(v.c_str(), &end);
+        else
+            *i = (int32_t)strtol(v.c_str(), &end, 10);
+        return end && *end == 0;
+    };
+    if (!number(v_min_cov, false, nullptr, &min_cov) || !number(v_cov, true, &read_cov, nullptr) || !number(v_ploidy, false, nullptr, &ploidy) ||
+        !number(v_span, false, nullptr, &min_span) || !number(v_context, false, nullptr, &context) || !number(v_window, false, nullptr, &window))
+        return fail("an option's value is not a number");
+    if (v_min_cov.empty() == v_cov.empty()) return fail("exactly one of --min-coverage-reads and --read-coverage must be given");
+    if (!v_cov.empty()) {
+        if (ploidy <= 0) return fail("--read-coverage needs --ploidy > 0");
+        min_cov = (int32_t)(0.5 * read_cov / ploidy);
+    }
+    dh_dazz *da = nullptr, *db = nullptr;
+    if (dh_dazz_open(pos[0].c_str(), &da)) return fail(dh_last_error());
+    if (dh_dazz_open(pos[1].c_str(), &db)) return fail(dh_last_error());
+    const int32_t ncontigs = dh_dazz_nreads(da);
+    dh_la_set *set = nullptr;
+    if (dh_las_read(pos[2].c_str(), &set)) return fail(dh_last_error());
+    const int64_t n = dh_la_set_count(set);
+    if (n == 0) {  // (:151-159)
+        fprintf(stderr, "validate-regions: warning: empty reads-alignment %s\n", pos[2].c_str());
+        return 0;
+    }
+    std::vector<dh_la> las(dh_la_set_records(set), dh_la_set_records(set) + n);
+    for (dh_la &l : las) {  // ids of the opened views
+        l.aread -= dh_dazz_first_id(da);
+        l.bread -= dh_dazz_first_id(db);
+    }
+    // the regions of the contigs between the first and the last aread of the file (:259-271)
+    std::vector<int64_t> ptr((size_t)ncontigs + 1);
+    const int64_t cnt = dh_dazz_read_mask(da, pos[0].c_str(), pos[3].c_str(), ptr.data(), nullptr, 0);
+    if (cnt < 0) return fail("mask " + pos[3] + ": " + dh_last_error());
+    std::vector<int32_t> iv((size_t)(2 * cnt) + 2);
+    if (dh_dazz_read_mask(da, pos[0].c_str(), pos[3].c_str(), ptr.data(), iv.data(), cnt) < 0) return fail("mask " + pos[3] + ": " + dh_last_error());
+    std::vector<dh_region> regions;
+    for (int32_t c = std::max(0, las.front().aread); c < ncontigs && c <= las.back().aread; c++)
+        for (int64_t j = ptr[(size_t)c]; j < ptr[(size_t)c + 1]; j++) regions.push_back(dh_region{c, iv[(size_t)(2 * j)], iv[(size_t)(2 * j + 1)]});
+    dh_ctx *ctx = nullptr;
+    if (dh_ctx_create(0, nullptr, &ctx)) return fail(dh_last_error());
+    dh_region_result *res = nullptr;
+    if (dh_la_validate_regions(ctx, las.data(), n, dh_dazz_offsets(da), ncontigs, regions.data(), (int32_t)regions.size(), context, window,
+                               min_cov, min_span, &res))
+        return fail(dh_last_error());
+    const dh_region_report *rep = dh_region_result_reports(res);
+    const int64_t *span_off = dh_region_result_span_off(res);
+    const int32_t *span_ids = dh_region_result_span_ids(res);
+    const int32_t first_contig = dh_dazz_first_id(da) + 1, first_read = dh_dazz_first_id(db) + 1;  // the ids of the report are 1-based
+    for (size_t r = 0; r < regions.size(); r++) {
+        if (rep[r].is_valid && !report_all) continue;
+        printf("{\"region\":{\"contigId\":%d,\"begin\":%d,\"end\":%d},\"regionWithContext\":{\"contigId\":%d,\"begin\":%d,\"end\":%d},"
+               "\"isValid\":%s,\"numSpanningReads\":%d,\"spanningReadIds\":[",
+               regions[r].contig + first_contig, regions[r].begin, regions[r].end, regions[r].contig + first_contig, rep[r].ctx_begin,
+               rep[r].ctx_end, rep[r].is_valid ? "true" : "false", rep[r].num_spanning_reads);
+        for (int64_t k = span_off[r]; k < span_off[r + 1]; k++) printf("%s%d", k > span_off[r] ? "," : "", span_ids[k] + first_read);
+        printf("],\"weakCoverageMaskBps\":%d}\n", rep[r].weak_bp);
+    }
+    if (!out_mask.empty()) {
+        static const int32_t no_iv[2] = {0, 0};
+        const int32_t *miv = dh_region_result_mask_count(res) > 0 ? dh_region_result_mask_iv(res) : no_iv;
+        if (dh_dazz_write_mask(pos[0].c_str(), out_mask.c_str(), ncontigs, dh_region_result_mask_ptr(res), miv)) return fail(dh_last_error());
+    }
+    dh_region_result_destroy(res);
+    dh_la_set_destroy(set);
+    dh_dazz_close(db);
+    dh_dazz_close(da);
+    dh_ctx_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     g_tool = argv[0];
@@ -1465,6 +1585,7 @@ int main(int argc, char **argv)
     if (g_tool == "fm-index") return tool_fm_index(args);
     if (g_tool == "chain-local-alignments") return tool_chain(args);
     if (g_tool == "propagate-mask") return tool_propagate_mask(args);
+    if (g_tool == "validate-regions") return tool_validate_regions(args);
     die("unknown tool (expected fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv "
         "computeintrinsicqv daccord merge-insertions)");
     return 1;
