@@ -6,7 +6,7 @@ CSRC := dentist_amd/csrc
 LIB := dentist_amd/libdentist_hip.so
 SIM := dentist_amd/sim/libdh_sim.so
 
-DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index chain-local-alignments propagate-mask validate-regions
+DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index chain-local-alignments propagate-mask validate-regions collect
 TOOLS := tools/daligner tools/damapper tools/datander tools/dazz_tools $(addprefix tools/,$(DAZZ_TOOLS))
 
 all: $(LIB) $(SIM) oracle $(TOOLS)
@@ -122,3 +122,13 @@ tests/native/libvreg_host.so: tests/native/vreg_host.cpp dentist_amd/csrc/dh_vre
 # would overrun
 tests/native/vreg_host_san: tests/native/vreg_host_main.cpp tests/native/vreg_host.cpp dentist_amd/csrc/dh_vreg.h include/dentist_hip.h
 	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/vreg_host_main.cpp tests/native/vreg_host.cpp
+
+# the lane code and the host plan of the collect filters (dentist_amd/csrc/dh_cfilt.h) compiled for the CPU: test infrastructure
+tests/native/libcfilt_host.so: tests/native/cfilt_host.cpp dentist_amd/csrc/dh_cfilt.h include/dentist_hip.h
+	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -o $@ $<
+
+# the same harness and a stand-alone main under the host sanitizers (a program of its own: nothing is preloaded); run it once
+# after a change to dh_cfilt.h -- the padded end of a read's order in the workgroup tiers, the last interval of a contig's mask
+# and the tier lists are where this code would overrun
+tests/native/cfilt_host_san: tests/native/cfilt_host_main.cpp tests/native/cfilt_host.cpp dentist_amd/csrc/dh_cfilt.h include/dentist_hip.h
+	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/cfilt_host_main.cpp tests/native/cfilt_host.cpp

@@ -120,6 +120,7 @@ SYMBOLS = [
     "dh_region_result_reports", "dh_region_result_weak_count", "dh_region_result_weak", "dh_region_result_span_off",
     "dh_region_result_span_ids", "dh_region_result_mask_ptr", "dh_region_result_mask_iv", "dh_region_result_mask_count",
     "dh_region_result_pairs", "dh_region_result_big_regions", "dh_region_result_groups",
+    "dh_la_collect_filter", "dh_la_set_collect_filter",
 ]
 
 _LIB = None
@@ -282,6 +283,8 @@ def lib():
         getattr(L, "dh_mask_result_" + name).restype = vp
     L.dh_mask_result_passes.argtypes = [vp]
     L.dh_mask_result_passes.restype = i32
+    L.dh_la_collect_filter.argtypes = [vp, vp, i64, vp, i32, vp, i32, vp, vp, ctypes.POINTER(ProcessOpts), vp, vp]
+    L.dh_la_set_collect_filter.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, ctypes.POINTER(ProcessOpts), vp, vp]
     L.dh_la_validate_regions.argtypes = [vp, vp, i64, vp, i32, vp, i32, i32, i32, i32, i32, ctypes.POINTER(vp)]
     L.dh_la_set_validate_regions.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, ctypes.POINTER(vp)]
     L.dh_region_result_destroy.argtypes = [vp]
@@ -625,6 +628,36 @@ class Context:
             arr = np.ascontiguousarray(las, dtype=LA_DTYPE)
             _check(lib().dh_la_validate_regions(self._h, arr.ctypes.data if len(arr) else None, len(arr), *tail))
         return ValidatedRegions(h, len(co) - 1)
+
+    def collect_filter(self, las, contig_off, read_off, opts, repeat_mask=None, inplace=False):
+        """dh_la_collect_filter: the six filters of `dentist collect` (filter.d:122-356) on the device; arguments and result of
+        the module-level collect_filter (the mask's intervals sorted and disjoint per contig).  `las` may be a raw handle of
+        align_db_block(..., raw=True) (dh_la_set_collect_filter): the flags are written into the set's records, a copy of which
+        is returned; the handle stays the caller's."""
+        co, ro = np.ascontiguousarray(contig_off, dtype=np.int64), np.ascontiguousarray(read_off, dtype=np.int64)
+        if len(co) < 1 or len(ro) < 1:
+            raise ValueError("contig_off and read_off need n + 1 entries")
+        dropped = np.zeros(6, dtype=np.int64)
+        used = np.ones(len(ro) - 1, dtype=np.uint8)
+        rp = ri = None
+        if repeat_mask is not None:
+            rp = np.ascontiguousarray(repeat_mask[0], dtype=np.int64)
+            ri = np.ascontiguousarray(np.concatenate([np.asarray(repeat_mask[1], dtype=np.int32).reshape(-1), [0, 0]]), dtype=np.int32)
+        tail = (co.ctypes.data, len(co) - 1, ro.ctypes.data, len(ro) - 1, rp.ctypes.data if rp is not None else None,
+                ri.ctypes.data if ri is not None else None, ctypes.byref(opts), dropped.ctypes.data, used.ctypes.data)
+        L = lib()
+        if isinstance(las, ctypes.c_void_p):
+            _check(L.dh_la_set_collect_filter(self._h, las, *tail))
+            n = L.dh_la_set_count(las)
+            arr = np.zeros(n, dtype=LA_DTYPE)
+            if n:
+                ctypes.memmove(arr.ctypes.data, L.dh_la_set_records(las), n * LA_DTYPE.itemsize)
+            return arr, dropped, used
+        arr = np.ascontiguousarray(las, dtype=LA_DTYPE)
+        if not inplace or arr is not las or not arr.flags.writeable:
+            arr = arr.copy()
+        _check(L.dh_la_collect_filter(self._h, arr.ctypes.data if len(arr) else None, len(arr), *tail))
+        return arr, dropped, used
 
     def transpose(self, A, B, las, trace=None, tspace=None, select_best=False):
         """dh_la_transpose: the same alignments with the roles of the sequences exchanged (aread = B read, trace points on

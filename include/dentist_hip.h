@@ -977,6 +977,48 @@ int64_t dh_region_result_pairs(const dh_region_result *r);        /* (record, re
 int64_t dh_region_result_big_regions(const dh_region_result *r);  /* regions whose difference array took the slab (tests) */
 int64_t dh_region_result_groups(const dh_region_result *r);       /* launch groups (tests) */
 
+/* ---- the alignment filters of `dentist collect` on the device (collectPileUps/filter.d:122-356 in the order of
+ *      collectPileUps/package.d:130-141); tools/collect is the drop-in of the command.  Kernels: csrc/dh_cfilt.hip.
+ *   Contract.  The result is that of dh_collect_filter above on the same input: DH_FLAG_DISABLED of every record, dropped6 (chains
+ *      per stage, not records), read_used[nreads].  A unit is an alignment chain: a record continues the chain of the record
+ *      before it iff it has NEXT without START and the same aread, bread and strand.  The unit has the first member's fields,
+ *      aepos / bepos of the last, diffs summed, covered = the sum of aepos - abpos over the members, and is disabled on entry iff
+ *      a member is; such a unit is skipped by every stage, never counted, and never makes a read ambiguous or redundant.
+ *      Per unit, judged by the first stage it fails: LQ iff (int64)diffs * 10^6 > (int64)max_align_err_ppm * covered; Improper
+ *      unless (abpos <= allowance || bbpos <= allowance) && (aepos + allowance >= alen || bepos + allowance >= blen);
+ *      WeaklyAnchored iff unmasked <= min_anchor, unmasked = the union of the members' A intervals minus the contig's mask (the
+ *      members in record order with the host's running `done` position).  Per read, over all units of one bread: Contained -- the
+ *      units sorted by (aread, abpos, bbpos, aepos, bepos, place in the input); for every enabled x the units y behind it are
+ *      scanned while y has x's aread and x.abpos <= y.abpos && y.aepos <= x.aepos (the first y that does not ends the scan), and
+ *      an enabled y of x's strand whose forward read interval lies inside x's is dropped; Ambiguous -- two enabled units whose
+ *      forward read intervals intersect drop every unit of the read (counted: those still enabled) and clear read_used;
+ *      Redundant -- an enabled unit with bbpos <= abpos && aepos + blen - bepos < alen does the same.  read_used is 1 for every
+ *      other read.
+ *   Input.  Records in any order in which the members of a chain are consecutive (grouped by read, or LAsort order by contig).
+ *      rep_ptr[ncontigs + 1] / rep_iv: the repeat mask (rep_ptr may be NULL: no mask); unlike the host function this one needs
+ *      the intervals of a contig sorted and disjoint (touching is allowed), the layout documented for every mask here.
+ *      dropped6 and read_used may be NULL.  The first form is in place; the second writes the flags into the set's records
+ *      (which must be on the host).
+ *   Refusals, made on the host before anything is launched or written (las is untouched): DH_EINVAL "bad argument" for a NULL
+ *      pointer, a negative count or opts missing; DH_EINVAL naming the lowest record with aread or bread out of range; DH_EINVAL
+ *      naming the lowest contig whose mask is not sorted and disjoint or leaves the contig; DH_EOVERFLOW for 2^30 records or
+ *      more.  n == 0 is no error: zeros, read_used all 1, no launch.
+ *   How.  One lane per record finds the chain starts, a scan numbers the chains; one lane per chain walks its members (two
+ *      binary searches per member into the prefix sums of the mask's interval lengths) and judges stages 1-3; the chains are
+ *      grouped by read (histogram, scan, scatter -- for either input order); a read of one unit is one lane's, of 2..64 one
+ *      wavefront's (in registers), of up to DH_CFILT_LDS_UNITS one workgroup's with the order of its units in LDS, of more the
+ *      same code on a slab of global memory.  No read falls back to the host.  32 bytes per record go up, one byte per record,
+ *      one per read and six counts come back.  The result does not depend on the knob and is the same from run to run.
+ *      Development knob (tests): DH_CFILT_LDS_UNITS, 64 .. 8192 (default 8192).
+ *   Unpinned.  Nothing: every record, count and read_used byte is pinned to dh_collect_filter (tests/test_parity_cfilter_gpu.py),
+ *      which tests/test_collect_filters.py pins to the oracle. */
+int dh_la_collect_filter(dh_ctx *ctx, dh_la *las, int64_t n, const int64_t *contig_off, int32_t ncontigs, const int64_t *read_off,
+                         int32_t nreads, const int64_t *rep_ptr, const int32_t *rep_iv, const dh_process_opts *opts,
+                         int64_t *dropped6, uint8_t *read_used);
+int dh_la_set_collect_filter(dh_ctx *ctx, dh_la_set *set, const int64_t *contig_off, int32_t ncontigs, const int64_t *read_off,
+                             int32_t nreads, const int64_t *rep_ptr, const int32_t *rep_iv, const dh_process_opts *opts,
+                             int64_t *dropped6, uint8_t *read_used);
+
 /* ---- gap-closed assembly writer (host only): the linear-scaffold subset of `dentist output`
  *      (source/dentist/commands/output.d:743-925): header "<id>\tscaffold-<first contig id>", contig
  *      slices lower case, insertions upper case (highlight != 0), unclosed gaps as 'n' runs, lines

@@ -53,6 +53,12 @@
 //                                    one JSON line per invalid region (per region with --report-all) of the mask <regions-mask>
 //                                    of <ref-db>, the weak-coverage mask written on request (dh_la_validate_regions: `dentist
 //                                    validate-regions`, commands/validateRegions.d:141-512; snakemake/Snakefile:1425-1466)
+//   collect [--mask=<name>[,<name>...]]... [--max-alignment-error=<f>] [--min-anchor-length=<n>] [--proper-alignment-allowance=<n>]
+//           [--min-spanning-reads=<n>] [--best-pile-up-margin=<f>] [--existing-gap-bonus=<f>] [--no-merge-extension]
+//           <ref-db> <reads-db> <ref-vs-reads.las> <pile-ups.db>
+//                                    the alignments filtered on the device (dh_la_collect_filter), the scaffold graph with its
+//                                    bubbles resolved, every pile-up written to <pile-ups.db> (`dentist collect`,
+//                                    commands/collectPileUps/package.d:88-206; snakemake/Snakefile:1257-1290)
 // DENTIST only sees exit codes, files and stdout of these tools; flags it never emits are rejected.
 #include <algorithm>
 #include <cmath>
@@ -1348,6 +1354,42 @@ static int tool_chain(const std::vector<std::string> &args)
     return 0;
 }
 
+// readMasks (propagateMask.d:136-142, collectPileUps/package.d:100-110): the union of the mask tracks `masks` of the opened DB,
+// per contig sorted with intersecting or touching intervals merged.  Returns "" or what failed.
+static std::string read_united_masks(const dh_dazz *da, const std::string &db_path, const std::vector<std::string> &masks,
+                                     std::vector<int64_t> &mask_ptr, std::vector<int32_t> &mask_iv)
+{
+    const int32_t ncontigs = dh_dazz_nreads(da);
+    std::vector<std::vector<std::pair<int32_t, int32_t>>> per((size_t)ncontigs);
+    for (const std::string &m : masks) {
+        std::vector<int64_t> ptr((size_t)ncontigs + 1);
+        const int64_t cnt = dh_dazz_read_mask(da, db_path.c_str(), m.c_str(), ptr.data(), nullptr, 0);
+        if (cnt < 0) return "mask " + m + ": " + dh_last_error();
+        std::vector<int32_t> iv((size_t)(2 * cnt) + 2);
+        if (dh_dazz_read_mask(da, db_path.c_str(), m.c_str(), ptr.data(), iv.data(), cnt) < 0) return "mask " + m + ": " + dh_last_error();
+        for (int32_t c = 0; c < ncontigs; c++)
+            for (int64_t j = ptr[(size_t)c]; j < ptr[(size_t)c + 1]; j++)
+                if (iv[(size_t)(2 * j + 1)] > iv[(size_t)(2 * j)]) per[(size_t)c].push_back({iv[(size_t)(2 * j)], iv[(size_t)(2 * j + 1)]});
+    }
+    mask_ptr.assign(1, 0);
+    mask_iv.clear();
+    for (auto &v : per) {
+        std::sort(v.begin(), v.end());
+        size_t first = mask_iv.size();
+        for (const auto &x : v) {
+            if (mask_iv.size() > first && x.first <= mask_iv.back())
+                mask_iv.back() = std::max(mask_iv.back(), x.second);
+            else {
+                mask_iv.push_back(x.first);
+                mask_iv.push_back(x.second);
+            }
+        }
+        mask_ptr.push_back((int64_t)mask_iv.size() / 2);
+    }
+    mask_iv.push_back(0);  // (never an empty array)
+    return "";
+}
+
 // ---------------------------------------------------------------------------------- propagate-mask
 // Unknown options: the usage text and exit 1.  Everything else that fails: the library's message and exit 2.
 static int tool_propagate_mask(const std::vector<std::string> &args)
@@ -1384,34 +1426,10 @@ static int tool_propagate_mask(const std::vector<std::string> &args)
     if (pos.size() == 4 && dh_dazz_open(pos[1].c_str(), &db)) return fail(dh_last_error());
     const dh_dazz *dest = db ? db : da;
     const int32_t ncontigs = dh_dazz_nreads(da), nreads = dh_dazz_nreads(dest);
-    // readMasks (:136-142): the union of the input masks, per contig sorted with intersecting or touching intervals merged
-    std::vector<std::vector<std::pair<int32_t, int32_t>>> per((size_t)ncontigs);
-    for (const std::string &m : masks) {
-        std::vector<int64_t> ptr((size_t)ncontigs + 1);
-        const int64_t cnt = dh_dazz_read_mask(da, pos[0].c_str(), m.c_str(), ptr.data(), nullptr, 0);
-        if (cnt < 0) return fail("mask " + m + ": " + dh_last_error());
-        std::vector<int32_t> iv((size_t)(2 * cnt) + 2);
-        if (dh_dazz_read_mask(da, pos[0].c_str(), m.c_str(), ptr.data(), iv.data(), cnt) < 0) return fail("mask " + m + ": " + dh_last_error());
-        for (int32_t c = 0; c < ncontigs; c++)
-            for (int64_t j = ptr[(size_t)c]; j < ptr[(size_t)c + 1]; j++)
-                if (iv[(size_t)(2 * j + 1)] > iv[(size_t)(2 * j)]) per[(size_t)c].push_back({iv[(size_t)(2 * j)], iv[(size_t)(2 * j + 1)]});
-    }
-    std::vector<int64_t> mask_ptr{0};
+    std::vector<int64_t> mask_ptr;
     std::vector<int32_t> mask_iv;
-    for (auto &v : per) {
-        std::sort(v.begin(), v.end());
-        size_t first = mask_iv.size();
-        for (const auto &x : v) {
-            if (mask_iv.size() > first && x.first <= mask_iv.back())
-                mask_iv.back() = std::max(mask_iv.back(), x.second);
-            else {
-                mask_iv.push_back(x.first);
-                mask_iv.push_back(x.second);
-            }
-        }
-        mask_ptr.push_back((int64_t)mask_iv.size() / 2);
-    }
-    mask_iv.push_back(0);  // (never an empty array)
+    const std::string mask_err = read_united_masks(da, pos[0], masks, mask_ptr, mask_iv);
+    if (!mask_err.empty()) return fail(mask_err);
     dh_la_set *set = nullptr;
     if (dh_las_read(in.c_str(), &set)) return fail(dh_last_error());
     const int64_t n = dh_la_set_count(set);
@@ -1551,6 +1569,163 @@ static int tool_validate_regions(const std::vector<std::string> &args)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- collect
+// `dentist collect` (collectPileUps/package.d:88-206): the six alignment filters on the device, the scaffold graph with
+// resolveBubbles, every pile-up written to <pile-ups.db>.  Unknown options: the usage text and exit 1.  Everything else that
+// fails: the library's message and exit 2.
+static int tool_collect(const std::vector<std::string> &args)
+{
+    const char *usage = "usage: collect [--mask=<name>[,<name>...]]... [--max-alignment-error=<f>] [--min-anchor-length=<n>] "
+                        "[--proper-alignment-allowance=<n>] [--min-spanning-reads=<n>] [--best-pile-up-margin=<f>] "
+                        "[--existing-gap-bonus=<f>] [--no-merge-extension] <ref-db> <reads-db> <ref-vs-reads.las> <pile-ups.db>";
+    auto fail = [](const std::string &what) {
+        fprintf(stderr, "collect: %s\n", what.c_str());
+        return 2;
+    };
+    std::vector<std::string> pos, masks;
+    std::string v_err, v_anchor, v_allow, v_span, v_margin, v_bonus, unused;
+    bool ignored = false, merge_extensions = true;
+    auto value = [](const std::string &a, const char *key, std::string *out) {
+        const size_t k = strlen(key);
+        if (a.size() <= k || a.compare(0, k, key) != 0) return false;
+        *out = a.substr(k);
+        return true;
+    };
+    auto add_masks = [&](const std::string &list) {  // <name>[,<name>...]
+        size_t at = 0;
+        while (at <= list.size()) {
+            const size_t comma = std::min(list.find(',', at), list.size());
+            if (comma > at) masks.push_back(list.substr(at, comma - at));
+            at = comma + 1;
+        }
+    };
+    for (size_t i = 0; i < args.size(); i++) {
+        const std::string &a = args[i];
+        std::string v;
+        if ((a == "-m" || a == "-e") && i + 1 < args.size()) {
+            if (a == "-m")
+                add_masks(args[++i]);
+            else
+                v_err = args[++i];
+        } else if (value(a, "--mask=", &v) || (a.compare(0, 2, "--") != 0 && value(a, "-m", &v)))
+            add_masks(v);
+        else if (value(a, "--max-alignment-error=", &v_err) || (a.compare(0, 2, "--") != 0 && value(a, "-e", &v_err)) ||
+                 value(a, "--min-anchor-length=", &v_anchor) || value(a, "--proper-alignment-allowance=", &v_allow) ||
+                 value(a, "--min-spanning-reads=", &v_span) || value(a, "--best-pile-up-margin=", &v_margin) ||
+                 value(a, "--existing-gap-bonus=", &v_bonus))
+            continue;
+        else if (a == "--no-merge-extension")
+            merge_extensions = false;
+        else if (a == "-v" || a == "--quiet" || value(a, "--config=", &unused) || value(a, "--threads=", &unused) ||
+                 value(a, "--auxiliary-threads=", &unused) || value(a, "--tmpdir=", &unused) || value(a, "--damapper-ref-vs-reads=", &unused) ||
+                 (a.compare(0, 2, "--") != 0 && (value(a, "-T", &unused) || value(a, "-A", &unused) || value(a, "-P", &unused))))
+            ignored = true;
+        else if (a.size() > 1 && a[0] == '-')
+            die("unknown or malformed option " + a + "\n" + usage);
+        else
+            pos.push_back(a);
+    }
+    if (masks.empty() || pos.size() != 4) die(usage);  // (at least one mask: commandline.d:1789)
+    if (ignored)
+        fprintf(stderr, "collect: --config, -v, --quiet, -T / --threads, -A / --auxiliary-threads, -P / --tmpdir and --damapper-ref-vs-reads have "
+                        "no effect here\n");
+    dh_la_set *set = nullptr;
+    if (dh_las_read(pos[2].c_str(), &set)) return fail(dh_last_error());
+    const int64_t n = dh_la_set_count(set);
+    if (n == 0) return fail("empty ref vs. reads alignment");  // (:127)
+    const int32_t tspace = dh_la_set_tspace(set);
+    // the defaults of commandline.d:1336, 1681, 1799-1808, 2024-2036, 2183, 2317-2332
+    double max_err = 0.3;
+    int32_t min_anchor = 500, allowance = tspace;
+    dh_scaffold_opts so;
+    dh_default_scaffold_opts(&so);
+    so.min_spanning_reads = 3, so.best_pile_up_margin = 3.0, so.existing_gap_bonus = 6.0, so.merge_extensions = merge_extensions ? 1 : 0;
+    auto number = [](const std::string &v, bool real, double *d, int32_t *i) {
+        if (v.empty()) return true;
+        char *end = nullptr;
+        if (real)
+            *d = strtod(v.c_str(), &end);
+        else
+            *i = (int32_t)strtol(v.c_str(), &end, 10);
+        return end && *end == 0;
+    };
+    if (!number(v_err, true, &max_err, nullptr) || !number(v_anchor, false, nullptr, &min_anchor) || !number(v_allow, false, nullptr, &allowance) ||
+        !number(v_span, false, nullptr, &so.min_spanning_reads) || !number(v_margin, true, &so.best_pile_up_margin, nullptr) ||
+        !number(v_bonus, true, &so.existing_gap_bonus, nullptr))
+        return fail("an option's value is not a number");
+    if (!(max_err > 0 && max_err <= 0.3)) return fail("--max-alignment-error must lie in (0, 0.3]");
+    dh_dazz *da = nullptr, *db = nullptr;
+    if (dh_dazz_open(pos[0].c_str(), &da)) return fail(dh_last_error());
+    if (dh_dazz_open(pos[1].c_str(), &db)) return fail(dh_last_error());
+    const int32_t ncontigs = dh_dazz_nreads(da), nreads = dh_dazz_nreads(db);
+    std::vector<int64_t> mask_ptr;
+    std::vector<int32_t> mask_iv;
+    const std::string mask_err = read_united_masks(da, pos[0], masks, mask_ptr, mask_iv);
+    if (!mask_err.empty()) return fail(mask_err);
+    std::vector<dh_la> las(dh_la_set_records(set), dh_la_set_records(set) + n);
+    for (dh_la &l : las) {  // ids of the opened views
+        l.aread -= dh_dazz_first_id(da);
+        l.bread -= dh_dazz_first_id(db);
+    }
+    dh_ctx *ctx = nullptr;
+    if (dh_ctx_create(0, nullptr, &ctx)) return fail(dh_last_error());
+    dh_process_opts po;
+    dh_default_process_opts(&po);
+    po.max_align_err_ppm = (int32_t)llround(max_err * 1e6), po.allowance = allowance, po.min_anchor = min_anchor;
+    int64_t dropped[6];
+    if (dh_la_collect_filter(ctx, las.data(), n, dh_dazz_offsets(da), ncontigs, dh_dazz_offsets(db), nreads, mask_ptr.data(), mask_iv.data(), &po,
+                             dropped, nullptr))
+        return fail(dh_last_error());
+    static const char *const stage[6] = {"LQ", "Improper", "WeaklyAnchored", "Contained", "Ambiguous", "Redundant"};
+    for (int k = 0; k < 6; k++) fprintf(stderr, "collect: filter %s dropped %lld alignment chains\n", stage[k], (long long)dropped[k]);
+    int64_t left = 0;
+    for (const dh_la &l : las) left += l.flags & DH_FLAG_DISABLED ? 0 : 1;
+    if (left == 0) return fail("no alignment chains left after filtering");  // (:153-156)
+    // the gaps of the input assembly: contigs that follow each other in one scaffold of the .dam (getScaffoldStructure)
+    std::vector<int32_t> gaps;
+    for (int32_t c = 0; c + 1 < ncontigs; c++)
+        if (dh_dazz_origin(da)[c + 1] > dh_dazz_origin(da)[c] && strcmp(dh_dazz_header(da, c), dh_dazz_header(da, c + 1)) == 0) {
+            gaps.push_back(c);
+            gaps.push_back(c + 1);
+        }
+    dh_db *A = nullptr, *B = nullptr;
+    if (dh_db_create(ctx, dh_dazz_bases(da), dh_dazz_offsets(da), ncontigs, nullptr, &A)) return fail(dh_last_error());
+    if (dh_db_create(ctx, dh_dazz_bases(db), dh_dazz_offsets(db), nreads, nullptr, &B)) return fail(dh_last_error());
+    dh_align_opts ao;
+    dh_default_align_opts(&ao);
+    ao.tspace = tspace;
+    dh_scaffold *sc = nullptr;
+    dh_la_set *extra = nullptr;
+    if (dh_scaffold_pileups_resolved(ctx, A, B, las.data(), n, gaps.data(), (int32_t)gaps.size() / 2, &so, &ao, allowance, 0, 0, &sc, &extra,
+                                     nullptr))
+        return fail(dh_last_error());
+    // the records and traces of *extra behind the file's: LA index n + i is record i of *extra
+    std::vector<uint16_t> trace(dh_la_set_trace(set), dh_la_set_trace(set) + dh_la_set_trace_len(set));
+    const int64_t nx = extra ? dh_la_set_count(extra) : 0;
+    for (int64_t i = 0; i < nx; i++) {
+        dh_la l = dh_la_set_records(extra)[i];
+        l.toff += (int64_t)trace.size();
+        las.push_back(l);
+    }
+    if (nx) trace.insert(trace.end(), dh_la_set_trace(extra), dh_la_set_trace(extra) + dh_la_set_trace_len(extra));
+    dh_pileups *piles = nullptr;
+    if (dh_scaffold_all_pileups(sc, las.data(), (int64_t)las.size(), 3, &piles, nullptr)) return fail(dh_last_error());
+    trace.push_back(0);  // (never an empty array)
+    if (dh_pileups_write_db(piles, las.data(), (int64_t)las.size(), trace.data(), dh_dazz_offsets(da), ncontigs, dh_dazz_offsets(db), nreads,
+                            tspace, pos[3].c_str()))
+        return fail(dh_last_error());
+    dh_pileups_destroy(piles);
+    if (extra) dh_la_set_destroy(extra);
+    dh_scaffold_destroy(sc);
+    dh_db_destroy(B);
+    dh_db_destroy(A);
+    dh_la_set_destroy(set);
+    dh_dazz_close(db);
+    dh_dazz_close(da);
+    dh_ctx_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     g_tool = argv[0];
@@ -1586,6 +1761,7 @@ int main(int argc, char **argv)
     if (g_tool == "chain-local-alignments") return tool_chain(args);
     if (g_tool == "propagate-mask") return tool_propagate_mask(args);
     if (g_tool == "validate-regions") return tool_validate_regions(args);
+    if (g_tool == "collect") return tool_collect(args);
     die("unknown tool (expected fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv "
         "computeintrinsicqv daccord merge-insertions)");
     return 1;
