@@ -41,7 +41,6 @@
 #endif
 
 #define CF_BLOCK 256          // threads of a workgroup
-#define CF_SCAN_ITEMS 4       // values per thread of a scan block
 #define CF_WAVE_UNITS 64      // a read of up to that many units is one wavefront's
 #define CF_LDS_UNITS 8192     // default (and largest) LDS cap: 32 KB of order per workgroup, five workgroups per CU of 160 KB
 
@@ -67,8 +66,8 @@ struct Mask {  // ptr == nullptr: no mask.  pre[j]: the bases of the intervals i
     const int32_t *iv;
     const int64_t *pre;
 };
-// the counters of a call (uint32 each)
-enum { C_UNITS = 0, C_WAVE = 1, C_LDS = 2, C_GLOBAL = 3, C_SLAB = 4, C_COUNT = 8 };
+// the counters of a call (uint32 each); the number of chains is the 64-bit total of the flag scan, kept behind the six counts
+enum { C_WAVE = 0, C_LDS = 1, C_GLOBAL = 2, C_SLAB = 3, C_COUNT = 4 };
 
 // dh_continues_chain (dh_internal.h)
 CF_HD bool continues(const Rec &prev, const Rec &cur)

@@ -1,9 +1,8 @@
 // dh_cfilt.hip -- the kernels of dh_la_collect_filter (lane code and layouts: dh_cfilt.h; driver: dh_cfilt.cpp).  gfx950, wave64.
 //
-//   k_cf_start          one lane per record: 1 iff it starts a chain.
-//   k_cf_reduce / k_cf_sums / k_cf_apply
-//                       the exclusive scan of 32-bit values: block sums (1024 values per block), their scan by one block with a
-//                       carry (which also stores the total), the scan inside the blocks.
+//   k_cf_start          one lane per record: 1 iff it starts a chain, written twice: the copy in uid is scanned in place.
+//   (dhk_scan_total / dhk_scan of dh_kernels.hip: the exclusive scans of the flags, whose 64-bit total is the number of chains,
+//   and of the per-read counts)
 //   k_cf_first          one lane per record: its unit (the scanned flags), and for a chain's first record the unit's first record.
 //   k_cf_unit           one lane per chain: cf::make_unit over its members, the stage of 1-3 it fails, +1 for its read.
 //   k_cf_scatter        one lane per chain: a slot of its read's segment (atomicAdd; the order reaches no result).
@@ -30,93 +29,33 @@ using cf::Unit;
 
 typedef unsigned long long u64;
 
-__global__ void __launch_bounds__(CF_BLOCK) k_cf_start(const Rec *__restrict__ recs, int64_t n, int32_t *__restrict__ flag)
+__global__ void __launch_bounds__(CF_BLOCK) k_cf_start(const Rec *__restrict__ recs, int64_t n, int32_t *__restrict__ flag, int32_t *__restrict__ uid)
 {
     const int64_t i = (int64_t)blockIdx.x * CF_BLOCK + threadIdx.x;
     if (i >= n) return;
-    flag[i] = i == 0 || !cf::continues(recs[i - 1], recs[i]) ? 1 : 0;
+    flag[i] = uid[i] = i == 0 || !cf::continues(recs[i - 1], recs[i]) ? 1 : 0;
 }
 
-// ---- the scan.  One value per thread over the block: *excl = the values in front of the thread's, returns all of them
-__device__ __forceinline__ int32_t block_scan(int32_t v, int32_t *ws, int32_t *excl)
-{
-    const int32_t lane = (int32_t)(threadIdx.x & 63), wave = (int32_t)(threadIdx.x >> 6);
-    for (int d = 1; d < 64; d <<= 1) {
-        const int32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    int32_t before = __shfl_up(v, 1, 64);
-    if (lane == 0) before = 0;
-    if (lane == 63) ws[wave] = v;
-    __syncthreads();
-    int32_t pre = 0, tot = 0;
-    for (int w = 0; w < CF_BLOCK / 64; w++) {
-        const int32_t x = ws[w];
-        if (w < wave) pre += x;
-        tot += x;
-    }
-    __syncthreads();  // (ws is written again by the next scan)
-    *excl = pre + before;
-    return tot;
-}
-__global__ void __launch_bounds__(CF_BLOCK) k_cf_reduce(const int32_t *__restrict__ in, int64_t m, int32_t *__restrict__ sums)
-{
-    __shared__ int32_t ws[CF_BLOCK / 64];
-    const int64_t base = ((int64_t)blockIdx.x * CF_BLOCK + threadIdx.x) * CF_SCAN_ITEMS;
-    int32_t v = 0;
-    for (int k = 0; k < CF_SCAN_ITEMS; k++) v += base + k < m ? in[base + k] : 0;
-    int32_t excl;
-    const int32_t tot = block_scan(v, ws, &excl);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(CF_BLOCK) k_cf_sums(int32_t *sums, int64_t nb, uint32_t *total)
-{
-    __shared__ int32_t ws[CF_BLOCK / 64];
-    int32_t carry = 0;
-    for (int64_t base = 0; base < nb; base += CF_BLOCK) {
-        const int64_t b = base + threadIdx.x;
-        const int32_t v = b < nb ? sums[b] : 0;
-        int32_t excl;
-        const int32_t tot = block_scan(v, ws, &excl);
-        if (b < nb) sums[b] = carry + excl;
-        carry += tot;
-    }
-    if (threadIdx.x == 0 && total) *total = (uint32_t)carry;
-}
-__global__ void __launch_bounds__(CF_BLOCK) k_cf_apply(const int32_t *in, int64_t m, const int32_t *__restrict__ sums, int32_t *out)
-{
-    __shared__ int32_t ws[CF_BLOCK / 64];
-    const int64_t base = ((int64_t)blockIdx.x * CF_BLOCK + threadIdx.x) * CF_SCAN_ITEMS;
-    int32_t x[CF_SCAN_ITEMS], v = 0;
-    for (int k = 0; k < CF_SCAN_ITEMS; k++) v += x[k] = base + k < m ? in[base + k] : 0;
-    int32_t excl;
-    block_scan(v, ws, &excl);
-    int32_t at = sums[blockIdx.x] + excl;
-    for (int k = 0; k < CF_SCAN_ITEMS; k++) {
-        if (base + k < m) out[base + k] = at;
-        at += x[k];
-    }
-}
-
-// flag: 1 for a chain's first record; uid: in the exclusive scan of flag, out the unit of every record
+// flag: 1 for a chain's first record; uid: in the exclusive scan of flag, out the unit of every record; nunits: the number of
+// chains (the scan's total; below 2^30, as the records are)
 __global__ void __launch_bounds__(CF_BLOCK)
-k_cf_first(const int32_t *__restrict__ flag, int32_t *uid, int64_t n, const uint32_t *__restrict__ ctr, int32_t *__restrict__ first)
+k_cf_first(const int32_t *__restrict__ flag, int32_t *uid, int64_t n, const u64 *__restrict__ nunits, int32_t *__restrict__ first)
 {
     const int64_t i = (int64_t)blockIdx.x * CF_BLOCK + threadIdx.x;
     if (i >= n) return;
     const int32_t u = uid[i] + flag[i] - 1;
     uid[i] = u;
     if (flag[i]) first[u] = (int32_t)i;
-    if (i == n - 1) first[ctr[cf::C_UNITS]] = (int32_t)n;
+    if (i == n - 1) first[*nunits] = (int32_t)n;
 }
 
 __global__ void __launch_bounds__(CF_BLOCK)
-k_cf_unit(const Rec *__restrict__ recs, int64_t n, const uint32_t *__restrict__ ctr, const int32_t *__restrict__ first, Mask mask,
+k_cf_unit(const Rec *__restrict__ recs, int64_t n, const u64 *__restrict__ nunits, const int32_t *__restrict__ first, Mask mask,
           const int32_t *__restrict__ alen, const int32_t *__restrict__ blen, Opts o, Unit *__restrict__ units, uint8_t *__restrict__ why,
           int32_t *cnt)
 {
     const int64_t u = (int64_t)blockIdx.x * CF_BLOCK + threadIdx.x;
-    const int64_t nu = (int64_t)ctr[cf::C_UNITS];
+    const int64_t nu = (int64_t)*nunits;
     if (u >= nu) return;
     Unit x;
     why[u] = cf::make_unit(recs, first[u], first[u + 1], nu == n, mask, alen, blen, o, &x);
@@ -126,11 +65,11 @@ k_cf_unit(const Rec *__restrict__ recs, int64_t n, const uint32_t *__restrict__ 
 
 // goff: the scanned counts (the first slot of every read); cur: the slots claimed so far
 __global__ void __launch_bounds__(CF_BLOCK)
-k_cf_scatter(const Unit *__restrict__ units, const uint32_t *__restrict__ ctr, const int32_t *__restrict__ goff, int32_t *cur,
+k_cf_scatter(const Unit *__restrict__ units, const u64 *__restrict__ nunits, const int32_t *__restrict__ goff, int32_t *cur,
              int32_t *__restrict__ gidx)
 {
     const int64_t u = (int64_t)blockIdx.x * CF_BLOCK + threadIdx.x;
-    if (u >= (int64_t)ctr[cf::C_UNITS]) return;
+    if (u >= (int64_t)*nunits) return;
     const int32_t r = units[u].bread;
     gidx[goff[r] + atomicAdd(cur + r, 1)] = (int32_t)u;
 }
@@ -288,31 +227,22 @@ k_cf_finish(const int32_t *__restrict__ flag, const int32_t *__restrict__ uid, i
 // n < 2^30 (the driver refuses more): every grid stays far below 2^31 blocks
 static inline dim3 cf_grid(int64_t m, int64_t per_block) { return dim3((unsigned)((m + per_block - 1) / per_block)); }
 
-extern "C" void dhk_cf_start(hipStream_t st, const Rec *recs, int64_t n, int32_t *flag)
+extern "C" void dhk_cf_start(hipStream_t st, const Rec *recs, int64_t n, int32_t *flag, int32_t *uid)
 {
-    if (n > 0) hipLaunchKernelGGL(k_cf_start, cf_grid(n, CF_BLOCK), dim3(CF_BLOCK), 0, st, recs, n, flag);
+    if (n > 0) hipLaunchKernelGGL(k_cf_start, cf_grid(n, CF_BLOCK), dim3(CF_BLOCK), 0, st, recs, n, flag, uid);
 }
-// out[i] = in[0] + .. + in[i - 1] (out may be in); sums: (m + 1023) / 1024 entries; total (may be NULL) gets the sum of all
-extern "C" void dhk_cf_scan(hipStream_t st, const int32_t *in, int32_t *out, int64_t m, int32_t *sums, uint32_t *total)
-{
-    const int64_t per = (int64_t)CF_BLOCK * CF_SCAN_ITEMS, nb = (m + per - 1) / per;
-    if (m <= 0) return;
-    hipLaunchKernelGGL(k_cf_reduce, dim3((unsigned)nb), dim3(CF_BLOCK), 0, st, in, m, sums);
-    hipLaunchKernelGGL(k_cf_sums, dim3(1), dim3(CF_BLOCK), 0, st, sums, nb, total);
-    hipLaunchKernelGGL(k_cf_apply, dim3((unsigned)nb), dim3(CF_BLOCK), 0, st, in, m, (const int32_t *)sums, out);
-}
-extern "C" void dhk_cf_units(hipStream_t st, const Rec *recs, int64_t n, const int32_t *flag, int32_t *uid, const uint32_t *ctr, int32_t *first,
+extern "C" void dhk_cf_units(hipStream_t st, const Rec *recs, int64_t n, const int32_t *flag, int32_t *uid, const u64 *nunits, int32_t *first,
                              Mask mask, const int32_t *alen, const int32_t *blen, Opts o, Unit *units, uint8_t *why, int32_t *cnt)
 {
-    hipLaunchKernelGGL(k_cf_first, cf_grid(n, CF_BLOCK), dim3(CF_BLOCK), 0, st, flag, uid, n, ctr, first);
-    hipLaunchKernelGGL(k_cf_unit, cf_grid(n, CF_BLOCK), dim3(CF_BLOCK), 0, st, recs, n, ctr, (const int32_t *)first, mask, alen, blen, o, units,
+    hipLaunchKernelGGL(k_cf_first, cf_grid(n, CF_BLOCK), dim3(CF_BLOCK), 0, st, flag, uid, n, nunits, first);
+    hipLaunchKernelGGL(k_cf_unit, cf_grid(n, CF_BLOCK), dim3(CF_BLOCK), 0, st, recs, n, nunits, (const int32_t *)first, mask, alen, blen, o, units,
                        why, cnt);
 }
 extern "C" void dhk_cf_group(hipStream_t st, const Unit *units, int64_t n, int32_t nreads, int32_t lds_units, const int32_t *goff, int32_t *cur,
-                             int32_t *gidx, uint8_t *why, uint8_t *used, uint32_t *ctr, int32_t *l_wave, int32_t *l_lds, int32_t *l_glob,
-                             uint32_t *slab_at)
+                             int32_t *gidx, uint8_t *why, uint8_t *used, const u64 *nunits, uint32_t *ctr, int32_t *l_wave, int32_t *l_lds,
+                             int32_t *l_glob, uint32_t *slab_at)
 {
-    hipLaunchKernelGGL(k_cf_scatter, cf_grid(n, CF_BLOCK), dim3(CF_BLOCK), 0, st, units, (const uint32_t *)ctr, goff, cur, gidx);
+    hipLaunchKernelGGL(k_cf_scatter, cf_grid(n, CF_BLOCK), dim3(CF_BLOCK), 0, st, units, nunits, goff, cur, gidx);
     hipLaunchKernelGGL(k_cf_classify, cf_grid(nreads, CF_BLOCK), dim3(CF_BLOCK), 0, st, units, goff, (const int32_t *)gidx, nreads, lds_units, why,
                        used, ctr, l_wave, l_lds, l_glob, slab_at);
 }

@@ -6,16 +6,14 @@
 // before the first launch); the compact nodes, the pair offsets and the tier lists are uploaded; every tier's kernel leaves a
 // State per node and the pair's record and chain counts; two exclusive scans place the pairs; the emission writes the result
 // arrays, which come back in one copy each.  src_index arrives as node numbers and is turned into record indices here.
-#include "dh_internal.h"
+#include "dh_host.h"
 
 #include <stdio.h>
 #include <stdlib.h>
 
-#include <chrono>
 #include <memory>
 
 #include "dh_chain.h"
-#include "dh_parallel.h"
 
 using chn::Key;
 using chn::Node;
@@ -32,7 +30,6 @@ extern "C" void dhk_chain_global(hipStream_t st, const Node *nodes, const int64_
 extern "C" void dhk_chain_emit(hipStream_t st, const Node *nodes, const State *state, const int64_t *pair_off, const int32_t *list,
                                int64_t nsingle, int64_t nmulti, const uint32_t *rec_at, const uint32_t *ch_at, Key *key, int64_t *off,
                                int32_t *sc, int64_t *src, uint32_t *flags);
-extern "C" void dhk_scan_total(hipStream_t st, uint32_t *v, int64_t n, uint32_t *sums, unsigned long long *total64);
 
 struct dh_la_chains {
     std::vector<int64_t> off{0}, src;
@@ -42,35 +39,6 @@ struct dh_la_chains {
 };
 static_assert(sizeof(dh_chain_opts) == 32 && sizeof(chn::Opts) == 32 && sizeof(Node) == 20 && sizeof(State) == 16,
               "the header states the layouts");
-
-namespace {
-
-template <typename T>
-int scr(dh_ctx *ctx, DhSlot id, size_t count, T **out)
-{
-    return dh_scratch(ctx, id, sizeof(T) * std::max<size_t>(count, 1), (void **)out);
-}
-
-template <typename T>
-int upload_vec(dh_ctx *ctx, DhSlot id, const std::vector<T> &v, T **out)
-{
-    if (int rc = scr(ctx, id, v.size(), out)) return rc;
-    if (!v.empty()) HIPCHK(hipMemcpyAsync(*out, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, ctx->stream));
-    return DH_OK;
-}
-
-int64_t env_knob(const char *name, int64_t dflt, int64_t lo, int64_t hi)
-{
-    if (const char *e = getenv(name)) return std::min<int64_t>(std::max<int64_t>(lo, atoll(e)), hi);  // development
-    return dflt;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-}  // namespace
 
 extern "C" void dh_default_chain_opts(dh_chain_opts *o, int32_t tspace)
 {
@@ -95,11 +63,11 @@ extern "C" int dh_la_chain(dh_ctx *ctx, const dh_la *las, int64_t n, const dh_ch
     if (o->max_indel < 0 || o->max_chain_gap < 0) return dh_fail(DH_EINVAL, "dh_la_chain: negative max_indel or max_chain_gap");
     const auto t_call = std::chrono::steady_clock::now();
     const bool trace = getenv("DH_TRACE") != nullptr;
-    const int64_t lds_cap = env_knob("DH_CHAIN_LDS_NODES", CH_LDS_NODES, CH_WAVE_NODES, CH_LDS_NODES);
-    const int64_t chunk_kb = env_knob("DH_CHAIN_CHUNK_KB", (int64_t)1 << 20, 1, (int64_t)1 << 26);
+    const int64_t lds_cap = dh_env_knob("DH_CHAIN_LDS_NODES", CH_LDS_NODES, CH_WAVE_NODES, CH_LDS_NODES);
+    const int64_t chunk_kb = dh_env_knob("DH_CHAIN_CHUNK_KB", (int64_t)1 << 20, 1, (int64_t)1 << 26);
     // ---- the plan, before anything is launched
     chn::Plan pl;
-    chn::build_plan(las, n, lds_cap, [](int64_t m, const std::function<void(int64_t, int64_t)> &fn) { dh_parallel_for(m, 1, fn); }, pl);
+    chn::build_plan(las, n, lds_cap, dh_plan_runner<1>, pl);  // (the plan runs one index per chunk of records)
     if (pl.bad >= 0) {
         char msg[200];
         snprintf(msg, sizeof(msg), "dh_la_chain: record %lld (aread %d, bread %d) precedes the enabled record before it: the input must be "
@@ -113,7 +81,7 @@ extern "C" int dh_la_chain(dh_ctx *ctx, const dh_la *las, int64_t n, const dh_ch
         *out = res.release();
         return DH_OK;
     }
-    const double ms_plan = ms_since(t_call);
+    const double ms_plan = dh_ms_since(t_call);
     const int64_t *tat = pl.tier_at;
     res->big_pairs = tat[chn::TIER_GLOBAL + 1] - tat[chn::TIER_GLOBAL];
     std::vector<int64_t> gat, woff;
@@ -129,17 +97,17 @@ extern "C" int dh_la_chain(dh_ctx *ctx, const dh_la *las, int64_t n, const dh_ch
     Key *d_key;
     uint32_t *d_cnt_rec, *d_cnt_ch, *d_sums;
     unsigned long long *d_total;
-    if (int rc = upload_vec(ctx, SLOT_CH_NODES, pl.nodes, &d_nodes)) return rc;
-    if (int rc = upload_vec(ctx, SLOT_CH_PAIR_OFF, pl.pair_off, &d_pair_off)) return rc;
-    if (int rc = upload_vec(ctx, SLOT_CH_LIST, pl.list, &d_list)) return rc;
-    if (int rc = upload_vec(ctx, SLOT_CH_WOFF, woff, &d_woff)) return rc;
-    if (int rc = scr(ctx, SLOT_CH_SLAB, (size_t)slab_words, &d_slab)) return rc;
-    if (int rc = scr(ctx, SLOT_CH_STATE, (size_t)nnodes, &d_state)) return rc;
-    if (int rc = scr(ctx, SLOT_CH_KEY, (size_t)nnodes, &d_key)) return rc;
-    if (int rc = scr(ctx, SLOT_CH_CNT_REC, (size_t)npairs + 1, &d_cnt_rec)) return rc;
-    if (int rc = scr(ctx, SLOT_CH_CNT_CH, (size_t)npairs + 1, &d_cnt_ch)) return rc;
-    if (int rc = scr(ctx, SLOT_CH_SUMS, (size_t)(npairs + 1) / 2048 + 1, &d_sums)) return rc;
-    if (int rc = scr(ctx, SLOT_CH_TOTAL, 2, &d_total)) return rc;
+    if (int rc = dh_upload(ctx, SLOT_CH_NODES, pl.nodes, &d_nodes)) return rc;
+    if (int rc = dh_upload(ctx, SLOT_CH_PAIR_OFF, pl.pair_off, &d_pair_off)) return rc;
+    if (int rc = dh_upload(ctx, SLOT_CH_LIST, pl.list, &d_list)) return rc;
+    if (int rc = dh_upload(ctx, SLOT_CH_WOFF, woff, &d_woff)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_CH_SLAB, (size_t)slab_words, &d_slab)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_CH_STATE, (size_t)nnodes, &d_state)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_CH_KEY, (size_t)nnodes, &d_key)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_CH_CNT_REC, (size_t)npairs + 1, &d_cnt_rec)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_CH_CNT_CH, (size_t)npairs + 1, &d_cnt_ch)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_CH_SUMS, (size_t)(npairs + 1) / 2048 + 1, &d_sums)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_CH_TOTAL, 2, &d_total)) return rc;
     HIPCHK(hipMemsetAsync(d_cnt_rec + npairs, 0, sizeof(uint32_t), st));
     HIPCHK(hipMemsetAsync(d_cnt_ch + npairs, 0, sizeof(uint32_t), st));
     HIPCHK(hipMemsetAsync(d_total, 0, 2 * sizeof(unsigned long long), st));
@@ -148,12 +116,12 @@ extern "C" int dh_la_chain(dh_ctx *ctx, const dh_la *las, int64_t n, const dh_ch
         HIPCHK(hipGetLastError());
         if (trace) {
             HIPCHK(hipStreamSynchronize(st));
-            ms_tier[t] = ms_since(t0);
+            ms_tier[t] = dh_ms_since(t0);
         }
         return DH_OK;
     };
     if (trace) HIPCHK(hipStreamSynchronize(st));
-    const double ms_upload = ms_since(t_call) - ms_plan;
+    const double ms_upload = dh_ms_since(t_call) - ms_plan;
     // ---- the tiers
     auto t0 = std::chrono::steady_clock::now();
     dhk_chain_single(st, d_nodes, d_pair_off, d_list + tat[0], tat[1] - tat[0], o, d_state, d_cnt_rec, d_cnt_ch);
@@ -183,10 +151,10 @@ extern "C" int dh_la_chain(dh_ctx *ctx, const dh_la *las, int64_t n, const dh_ch
     int64_t *d_off, *d_src;
     int32_t *d_score;
     uint32_t *d_flags;
-    if (int rc = scr(ctx, SLOT_CH_OUT_OFF, (size_t)nch, &d_off)) return rc;
-    if (int rc = scr(ctx, SLOT_CH_OUT_SCORE, (size_t)nch, &d_score)) return rc;
-    if (int rc = scr(ctx, SLOT_CH_OUT_SRC, (size_t)nrec, &d_src)) return rc;
-    if (int rc = scr(ctx, SLOT_CH_OUT_FLAGS, (size_t)nrec, &d_flags)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_CH_OUT_OFF, (size_t)nch, &d_off)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_CH_OUT_SCORE, (size_t)nch, &d_score)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_CH_OUT_SRC, (size_t)nrec, &d_src)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_CH_OUT_FLAGS, (size_t)nrec, &d_flags)) return rc;
     dhk_chain_emit(st, d_nodes, d_state, d_pair_off, d_list, tat[1], npairs - tat[1], d_cnt_rec, d_cnt_ch, d_key, d_off, d_score, d_src, d_flags);
     HIPCHK(hipGetLastError());
     res->off.resize((size_t)nch + 1);
@@ -201,7 +169,7 @@ extern "C" int dh_la_chain(dh_ctx *ctx, const dh_la *las, int64_t n, const dh_ch
     }
     HIPCHK(hipStreamSynchronize(st));
     res->off[(size_t)nch] = nrec;
-    const double ms_emit = ms_since(t0);
+    const double ms_emit = dh_ms_since(t0);
     int64_t *src = res->src.data();
     const int64_t *node_src = pl.node_src.data();
     dh_parallel_for(nrec, 1 << 16, [&](int64_t lo, int64_t hi) {
@@ -214,16 +182,17 @@ extern "C" int dh_la_chain(dh_ctx *ctx, const dh_la *las, int64_t n, const dh_ch
                 "%lld chains, %lld output records\n",
                 (long long)n, (long long)nnodes, (long long)npairs, (long long)(tat[1] - tat[0]), (long long)(tat[2] - tat[1]),
                 (long long)(tat[3] - tat[2]), (long long)lds_cap, (long long)(tat[4] - tat[3]), gat.size() - 1, ms_plan, ms_upload, ms_tier[0],
-                ms_tier[1], ms_tier[2], ms_tier[3], ms_emit, ms_since(t_call), (long long)nch, (long long)nrec);
+                ms_tier[1], ms_tier[2], ms_tier[3], ms_emit, dh_ms_since(t_call), (long long)nch, (long long)nrec);
     *out = res.release();
     return DH_OK;
 }
 
 extern "C" int dh_la_set_chain(dh_ctx *ctx, const dh_la_set *set, const dh_chain_opts *o, dh_la_chains **out)
 {
-    if (!set) return dh_fail(DH_EINVAL, "dh_la_set_chain: bad argument");
-    if (set->la.empty() && set->d_la_n > 0) return dh_fail(DH_EINVAL, "dh_la_set_chain: the set's records are on the device only");
-    return dh_la_chain(ctx, set->la.data(), (int64_t)set->la.size(), o, out);
+    const dh_la *las;
+    int64_t n;
+    if (int rc = dh_set_host_records("dh_la_set_chain", true, set, &las, &n)) return rc;  // (dh_la_chain checks the others)
+    return dh_la_chain(ctx, las, n, o, out);
 }
 
 extern "C" void dh_la_chains_destroy(dh_la_chains *c) { delete c; }

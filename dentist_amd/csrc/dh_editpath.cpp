@@ -9,7 +9,7 @@
 // dh_la_transpose / dh_la_set_transpose run the same chunks cut between records, leave the ops of a chunk on the device
 // and let k_trace_transpose put the trace points of every record's transposed path on the grid of the B read (the
 // SLOT_TR_* group); the host adds the coordinates, the chain flags and LAsort order.
-#include "dh_internal.h"
+#include "dh_host.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -40,12 +40,6 @@ extern "C" int64_t dh_edit_paths_general_tiles(const dh_edit_paths *p) { return 
 namespace {
 
 #define EP_GENERAL_BATCH 2048 /* tiles per launch of the full-matrix kernel: 64 KB of decisions each at tspace = 250 */
-
-template <typename T>
-int scr(dh_ctx *ctx, DhSlot id, size_t count, T **out)
-{
-    return dh_scratch(ctx, id, sizeof(T) * std::max<size_t>(count, 1), (void **)out);
-}
 
 // the tiles of record `idx` (dazzler.d:2405-2426: A from abpos to the next multiple of tspace, then in steps of tspace, the
 // last one ending at aepos; B the running sum of the trace's bbases), validated: nothing the kernels read lies outside
@@ -104,8 +98,7 @@ int cut_record(const dh_db *A, const dh_db *B, const dh_la &la, int64_t idx, con
 
 size_t edit_chunk()  // tiles per launch
 {
-    if (const char *e = getenv("DH_EDIT_CHUNK")) return (size_t)std::max(1, atoi(e));  // development
-    return 131072;
+    return (size_t)dh_env_knob("DH_EDIT_CHUNK", 131072, 1, INT32_MAX);  // development
 }
 
 struct ChunkRun {
@@ -150,10 +143,10 @@ int run_chunk(const ChunkRun &r, const std::vector<EpTile> &tiles, size_t t0, si
         EpTile *d_tiles;
         uint64_t *d_dm;
         EpResult *d_res;
-        if (int rc = scr(ctx, SLOT_EP_TILES, nfast, &d_tiles)) return rc;
-        if (int rc = scr(ctx, SLOT_EP_DM, dm1 + dm2, &d_dm)) return rc;
-        if (int rc = scr(ctx, SLOT_EP_OW, wbase[2] + n2 * (size_t)owords[2], &d_ow)) return rc;
-        if (int rc = scr(ctx, SLOT_EP_RES, nfast, &d_res)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_EP_TILES, nfast, &d_tiles)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_EP_DM, dm1 + dm2, &d_dm)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_EP_OW, wbase[2] + n2 * (size_t)owords[2], &d_ow)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_EP_RES, nfast, &d_res)) return rc;
         HIPCHK(hipMemcpyAsync(d_tiles, stage.data(), sizeof(EpTile) * nfast, hipMemcpyHostToDevice, st));
         dhk_edit_fast(st, 1, d_tiles, (int32_t)n1, ab, bf, brc, rows[1], owords[1], d_dm, d_ow, d_res);
         dhk_edit_fast(st, 2, d_tiles + n1, (int32_t)n2, ab, bf, brc, rows[2], owords[2], d_dm + dm1, d_ow + wbase[2], d_res + n1);
@@ -194,11 +187,11 @@ int run_chunk(const ChunkRun &r, const std::vector<EpTile> &tiles, size_t t0, si
         int64_t *d_goff;
         uint32_t *d_dm;
         EpResult *d_res;
-        if (int rc = scr(ctx, SLOT_EP_GEN_TILES, ng, &d_tiles)) return rc;
-        if (int rc = scr(ctx, SLOT_EP_GEN_DM, gb * (size_t)rows * 64, &d_dm)) return rc;
-        if (int rc = scr(ctx, SLOT_EP_GEN_OW, (size_t)goff[ng], &d_gow)) return rc;
-        if (int rc = scr(ctx, SLOT_EP_GEN_OFF, ng + 1, &d_goff)) return rc;
-        if (int rc = scr(ctx, SLOT_EP_GEN_RES, ng, &d_res)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_EP_GEN_TILES, ng, &d_tiles)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_EP_GEN_DM, gb * (size_t)rows * 64, &d_dm)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_EP_GEN_OW, (size_t)goff[ng], &d_gow)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_EP_GEN_OFF, ng + 1, &d_goff)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_EP_GEN_RES, ng, &d_res)) return rc;
         HIPCHK(hipMemcpyAsync(d_tiles, stage.data(), sizeof(EpTile) * ng, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_goff, goff.data(), sizeof(int64_t) * (ng + 1), hipMemcpyHostToDevice, st));
         for (size_t g0 = 0; g0 < ng; g0 += gb)  // (one stream: a batch starts when the one before it is done with d_dm)
@@ -224,8 +217,8 @@ int run_chunk(const ChunkRun &r, const std::vector<EpTile> &tiles, size_t t0, si
     if (total == 0) return DH_OK;
     EpCopy *d_cp;
     uint8_t *d_out;
-    if (int rc = scr(ctx, SLOT_EP_COPY, n, &d_cp)) return rc;
-    if (int rc = scr(ctx, SLOT_EP_OPS, (size_t)total, &d_out)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_EP_COPY, n, &d_cp)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_EP_OPS, (size_t)total, &d_out)) return rc;
     HIPCHK(hipMemcpyAsync(d_cp, cp.data(), sizeof(EpCopy) * n, hipMemcpyHostToDevice, st));
     dhk_edit_compact(st, d_cp, (int32_t)n, d_ow, d_gow, d_out);
     HIPCHK(hipGetLastError());
@@ -312,10 +305,10 @@ int transpose_chunk(const ChunkRun &r, const std::vector<EpTile> &tiles, const s
     uint2 *d_bound;
     uint32_t *d_pairs;
     int32_t *d_status;
-    if (int rc = scr(ctx, SLOT_TR_RECS, nrec, &d_recs)) return rc;
-    if (int rc = scr(ctx, SLOT_TR_BOUND, nslots, &d_bound)) return rc;
-    if (int rc = scr(ctx, SLOT_TR_PAIRS, nslots, &d_pairs)) return rc;
-    if (int rc = scr(ctx, SLOT_TR_STATUS, nrec, &d_status)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_TR_RECS, nrec, &d_recs)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_TR_BOUND, nslots, &d_bound)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_TR_PAIRS, nslots, &d_pairs)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_TR_STATUS, nrec, &d_status)) return rc;
     HIPCHK(hipMemcpyAsync(d_recs, recs.data(), sizeof(EpTrRec) * nrec, hipMemcpyHostToDevice, st));
     dhk_trace_transpose(st, d_recs, (int32_t)nrec, d_ops, r.ts, d_bound, d_pairs, d_status);
     HIPCHK(hipGetLastError());

@@ -141,9 +141,10 @@ enum DhSlot : int {
     SLOT_VR_SPAN_OUT, SLOT_VR_SLAB, SLOT_VR_RCNT, SLOT_VR_IV,
     // collect filters (dh_la_collect_filter, dh_cfilt.cpp): all live for one call.  The compact records, the contig and read lengths
     // and the mask with its prefix sums are the input; SLOT_CF_FLAG / UID / FIRST are per record (starts a chain, its unit, a unit's
-    // first record), SLOT_CF_SUMS the block sums of both scans, SLOT_CF_UNITS / WHY per chain; SLOT_CF_CNT (counts, then their scan),
+    // first record), SLOT_CF_SUMS the block sums of both scans (dhk_scan: one per 2048 values), SLOT_CF_UNITS / WHY per chain; SLOT_CF_CNT (counts, then their scan),
     // SLOT_CF_CUR and SLOT_CF_USED are per read, SLOT_CF_GIDX the units grouped by read; the tier lists, the slab offsets of the
-    // global tier and its slab; SLOT_CF_CTR the counters of the call, SLOT_CF_OUT a byte per record, SLOT_CF_CNT6 the six counts
+    // global tier and its slab; SLOT_CF_CTR the counters of the call, SLOT_CF_OUT a byte per record, SLOT_CF_CNT6 the six counts and, as a seventh 64-bit word, the
+    // number of chains (the total of the flag scan)
     SLOT_CF_RECS, SLOT_CF_ALEN, SLOT_CF_BLEN, SLOT_CF_MASK_PTR, SLOT_CF_MASK_IV, SLOT_CF_MASK_PRE, SLOT_CF_FLAG, SLOT_CF_UID, SLOT_CF_SUMS,
     SLOT_CF_FIRST, SLOT_CF_UNITS, SLOT_CF_WHY, SLOT_CF_CNT, SLOT_CF_CUR, SLOT_CF_GIDX, SLOT_CF_USED, SLOT_CF_OUT, SLOT_CF_CTR, SLOT_CF_CNT6,
     SLOT_CF_LWAVE, SLOT_CF_LLDS, SLOT_CF_LGLOB, SLOT_CF_SLAB_AT, SLOT_CF_SLAB,

@@ -9,15 +9,12 @@
 // buffer is scanned again in halves (a range of one word that still overflows grows the buffer to the counted number:
 // nothing is dropped).  The candidates the scan could not compare whole are cut into segments, one wavefront of
 // k_locate_verify each.  The survivors are sorted on the host by (query, strand, position).
-#include "dh_internal.h"
+#include "dh_host.h"
 
 #include <stdio.h>
 #include <stdlib.h>
 
-#include <chrono>
-
 #include "dh_locate.h"
-#include "dh_parallel.h"
 
 extern "C" void dhk_locate_scan(hipStream_t st, int use_bitmap, const uint64_t *text, int64_t nbases, int64_t w0, int64_t w1,
                                 const LocSlot *table, int32_t tbits, const uint32_t *bitmap, const uint32_t *memb, const LocPat *pats,
@@ -39,25 +36,14 @@ namespace {
 const size_t kStageBytes = 8u << 20;        // the page-locked staging buffer of the uploads
 const int64_t kUnitBatch = (int64_t)1 << 22;  // verify units per launch
 
-template <typename T>
-int scr(dh_ctx *ctx, DhSlot id, size_t count, T **out)
-{
-    return dh_scratch(ctx, id, sizeof(T) * std::max<size_t>(count, 1), (void **)out);
-}
-
-int64_t env_knob(const char *name, int64_t dflt, int64_t lo, int64_t hi)
-{
-    if (const char *e = getenv(name)) return std::min<int64_t>(std::max<int64_t>(lo, atoll(e)), hi);  // development
-    return dflt;
-}
-
 struct Stage {  // bounded staging of host arrays
     void *p = nullptr;
     ~Stage() { dh_pinned_free(p, kStageBytes); }
 };
 
-// a host array to the device through the staging buffer
-int upload(dh_ctx *ctx, Stage &sg, void *dst, const void *src, size_t bytes)
+// a host array to the device through the staging buffer, piece by piece with a wait behind each (not dh_upload: the
+// source is pageable and may be large)
+int upload_staged(dh_ctx *ctx, Stage &sg, void *dst, const void *src, size_t bytes)
 {
     for (size_t at = 0; at < bytes; at += kStageBytes) {
         const size_t n = std::min(kStageBytes, bytes - at);
@@ -69,15 +55,10 @@ int upload(dh_ctx *ctx, Stage &sg, void *dst, const void *src, size_t bytes)
 }
 
 template <typename T>
-int upload_vec(dh_ctx *ctx, Stage &sg, DhSlot id, const std::vector<T> &v, T **out)
+int upload_staged(dh_ctx *ctx, Stage &sg, DhSlot id, const std::vector<T> &v, T **out)
 {
-    if (int rc = scr(ctx, id, v.size(), out)) return rc;
-    return upload(ctx, sg, *out, v.data(), sizeof(T) * v.size());
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (int rc = dh_scr(ctx, id, v.size(), out)) return rc;
+    return upload_staged(ctx, sg, *out, v.data(), sizeof(T) * v.size());
 }
 
 // the reference bytes checked for a code above 3 without a device: first bad position or -1
@@ -138,7 +119,7 @@ extern "C" int dh_exact_locate(dh_ctx *ctx, const uint8_t *ref, const int64_t *r
     }
     loc::Plan pl;
     loc::build_plan(qry, qry_off, nqry, both_strands != 0, longest,
-                    [](int64_t n, const std::function<void(int64_t, int64_t)> &fn) { dh_parallel_for(n, 64, fn); }, pl);
+                    dh_plan_runner<64>, pl);
     if (pl.bad_query >= 0) {
         char msg[160];
         snprintf(msg, sizeof(msg), "dh_exact_locate: query %lld: a code above 3", (long long)pl.bad_query);
@@ -159,7 +140,7 @@ extern "C" int dh_exact_locate(dh_ctx *ctx, const uint8_t *ref, const int64_t *r
     if (!sg.p) return dh_fail(DH_ENOMEM, "dh_exact_locate: no staging buffer");
     const int64_t nwords = (nbases + 31) >> 5;
     uint64_t *d_text;
-    if (int rc = scr(ctx, SLOT_LOC_TEXT, (size_t)nwords + LOC_TEXT_PAD, &d_text)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_LOC_TEXT, (size_t)nwords + LOC_TEXT_PAD, &d_text)) return rc;
     const int64_t slice = (int64_t)(kStageBytes / 8);  // words
     for (int64_t w0 = 0; w0 < nwords; w0 += slice) {
         const int64_t n = std::min(slice, nwords - w0);
@@ -179,26 +160,26 @@ extern "C" int dh_exact_locate(dh_ctx *ctx, const uint8_t *ref, const int64_t *r
     uint32_t *d_memb, *d_bitmap;
     LocSlot *d_table;
     LocShort *d_shorts;
-    if (int rc = upload_vec(ctx, sg, SLOT_LOC_STARTS, starts, &d_starts)) return rc;
-    if (int rc = upload_vec(ctx, sg, SLOT_LOC_PW, pl.pw, &d_pw)) return rc;
-    if (int rc = upload_vec(ctx, sg, SLOT_LOC_PATS, pl.pats, &d_pats)) return rc;
-    if (int rc = upload_vec(ctx, sg, SLOT_LOC_MEMB, pl.memb, &d_memb)) return rc;
-    if (int rc = upload_vec(ctx, sg, SLOT_LOC_TABLE, pl.table, &d_table)) return rc;
-    if (int rc = upload_vec(ctx, sg, SLOT_LOC_BITMAP, pl.bitmap, &d_bitmap)) return rc;
-    if (int rc = upload_vec(ctx, sg, SLOT_LOC_SHORTS, pl.shorts, &d_shorts)) return rc;
-    const double ms_upload = ms_since(t_call);
+    if (int rc = upload_staged(ctx, sg, SLOT_LOC_STARTS, starts, &d_starts)) return rc;
+    if (int rc = upload_staged(ctx, sg, SLOT_LOC_PW, pl.pw, &d_pw)) return rc;
+    if (int rc = upload_staged(ctx, sg, SLOT_LOC_PATS, pl.pats, &d_pats)) return rc;
+    if (int rc = upload_staged(ctx, sg, SLOT_LOC_MEMB, pl.memb, &d_memb)) return rc;
+    if (int rc = upload_staged(ctx, sg, SLOT_LOC_TABLE, pl.table, &d_table)) return rc;
+    if (int rc = upload_staged(ctx, sg, SLOT_LOC_BITMAP, pl.bitmap, &d_bitmap)) return rc;
+    if (int rc = upload_staged(ctx, sg, SLOT_LOC_SHORTS, pl.shorts, &d_shorts)) return rc;
+    const double ms_upload = dh_ms_since(t_call);
     // the pre-filter in LDS is used while at most one bit in eight of it is set: measured it takes the scan of
     // 2 002 groups from 0.58 to 0.21 ms and changes nothing at 798 408 groups, where it is full.  DH_LOCATE_BITMAP forces it
     size_t ngroups = 0;
     for (const LocSlot &s : pl.table) ngroups += s.count != 0;
-    const int use_bitmap = (int)env_knob("DH_LOCATE_BITMAP", ngroups * 8 <= LOC_BITMAP_BITS ? 1 : 0, 0, 1);
+    const int use_bitmap = (int)dh_env_knob("DH_LOCATE_BITMAP", ngroups * 8 <= LOC_BITMAP_BITS ? 1 : 0, 0, 1);
     // ---- scan, verify
-    int64_t cap = env_knob("DH_LOCATE_CAND_CAP", LOC_CAND_CAP_DEFAULT, 1, (int64_t)1 << 31);
-    const int64_t seg = loc::round_seg(env_knob("DH_LOCATE_SEG", LOC_SEG_DEFAULT, 1, (int64_t)1 << 40));
+    int64_t cap = dh_env_knob("DH_LOCATE_CAND_CAP", LOC_CAND_CAP_DEFAULT, 1, (int64_t)1 << 31);
+    const int64_t seg = loc::round_seg(dh_env_knob("DH_LOCATE_SEG", LOC_SEG_DEFAULT, 1, (int64_t)1 << 40));
     LocCand *d_cands;
     unsigned long long *d_counter;
-    if (int rc = scr(ctx, SLOT_LOC_CANDS, (size_t)cap, &d_cands)) return rc;
-    if (int rc = scr(ctx, SLOT_LOC_COUNTER, 1, &d_counter)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_LOC_CANDS, (size_t)cap, &d_cands)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_LOC_COUNTER, 1, &d_counter)) return rc;
     std::vector<LocCand> all, part;
     std::vector<LocUnit> units;
     std::vector<std::pair<int64_t, int64_t>> todo{{0, nwords}};
@@ -219,7 +200,7 @@ extern "C" int dh_exact_locate(dh_ctx *ctx, const uint8_t *ref, const int64_t *r
         unsigned long long count = 0;
         HIPCHK(hipMemcpyAsync(&count, d_counter, sizeof(count), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        ms_scan += ms_since(t_scan);
+        ms_scan += dh_ms_since(t_scan);
         nranges++;
         if ((int64_t)count > cap) {
             if (r.second - r.first > 1) {  // the later half first on the stack, so that the ranges run in text order
@@ -229,7 +210,7 @@ extern "C" int dh_exact_locate(dh_ctx *ctx, const uint8_t *ref, const int64_t *r
             } else {  // one word of positions: the buffer grows to what was counted
                 if (count > 0xFFFFFFFFull) return dh_fail(DH_EOVERFLOW, "dh_exact_locate: more than 2^32 candidates at 32 positions");
                 cap = (int64_t)count;
-                if (int rc = scr(ctx, SLOT_LOC_CANDS, (size_t)cap, &d_cands)) return rc;
+                if (int rc = dh_scr(ctx, SLOT_LOC_CANDS, (size_t)cap, &d_cands)) return rc;
                 todo.push_back(r);
             }
             continue;
@@ -242,10 +223,10 @@ extern "C" int dh_exact_locate(dh_ctx *ctx, const uint8_t *ref, const int64_t *r
         loc::make_units(part.data(), (int64_t)count, pl, seg, units);
         if (!units.empty()) {
             LocUnit *d_units;
-            if (int rc = scr(ctx, SLOT_LOC_UNITS, (size_t)std::min<int64_t>((int64_t)units.size(), kUnitBatch), &d_units)) return rc;
+            if (int rc = dh_scr(ctx, SLOT_LOC_UNITS, (size_t)std::min<int64_t>((int64_t)units.size(), kUnitBatch), &d_units)) return rc;
             for (int64_t u0 = 0; u0 < (int64_t)units.size(); u0 += kUnitBatch) {
                 const int64_t n = std::min<int64_t>(kUnitBatch, (int64_t)units.size() - u0);
-                if (int rc = upload(ctx, sg, d_units, units.data() + u0, sizeof(LocUnit) * (size_t)n)) return rc;
+                if (int rc = upload_staged(ctx, sg, d_units, units.data() + u0, sizeof(LocUnit) * (size_t)n)) return rc;
                 dhk_locate_verify(st, d_text, nbases, d_pw, d_pats, d_cands, (int64_t)count, d_units, n, seg);
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipStreamSynchronize(st));  // (the staging buffer is written again by the next batch)
@@ -257,7 +238,7 @@ extern "C" int dh_exact_locate(dh_ctx *ctx, const uint8_t *ref, const int64_t *r
             if (c.ok) all.push_back(c);
         ncand_total += (int64_t)count;
         nunit_total += (int64_t)units.size();
-        ms_verify += ms_since(t_verify);
+        ms_verify += dh_ms_since(t_verify);
     }
     loc::finish(all, pl, starts.data(), nref, res->hits);
     if (trace)
@@ -265,7 +246,7 @@ extern "C" int dh_exact_locate(dh_ctx *ctx, const uint8_t *ref, const int64_t *r
                 "[locate] %lld bases in %lld records, %lld queries (%zu anchor groups, %zu short), bitmap %d: upload/pack %.2f ms, scan "
                 "%.2f ms (%lld ranges), verify %.2f ms (%lld candidates, %lld units), total %.2f ms, %zu hits\n",
                 (long long)nbases, (long long)nref, (long long)nqry, ngroups, pl.shorts.size(), use_bitmap, ms_upload, ms_scan,
-                (long long)nranges, ms_verify, (long long)ncand_total, (long long)nunit_total, ms_since(t_call), res->hits.size());
+                (long long)nranges, ms_verify, (long long)ncand_total, (long long)nunit_total, dh_ms_since(t_call), res->hits.size());
     *out = res.release();
     return DH_OK;
 }

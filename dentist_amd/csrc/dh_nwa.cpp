@@ -8,7 +8,7 @@
 // applies nwa::accepted to the cost it reports, and the pairs that fail run again, together, at twice the half-width -- in
 // launch groups bounded by the same knob, one launch per kernel class -- until the band would exceed NWA_MAX_W columns:
 // those get DH_NW_BAND_EXCEEDED.  k_edit_compact (dh_editpath.hip) puts the ops of a group in path order.
-#include "dh_internal.h"
+#include "dh_host.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,23 +27,14 @@ static_assert(NWA_MAX_LEN == DH_NWA_MAX_LEN && NWA_MAX_W == DH_NWA_MAX_BAND, "th
 
 const dh_nw_scoring kDefaultScoring = {5, -4, 16, 4};  // EDNAFULL, gapopen 16, gapextend 4: nucleotide stretcher
 
-template <typename T>
-int scr(dh_ctx *ctx, DhSlot id, size_t count, T **out)
-{
-    return dh_scratch(ctx, id, sizeof(T) * std::max<size_t>(count, 1), (void **)out);
-}
-
 int64_t nwa_budget_words()  // decision words (64 bits) per launch group
 {
-    int64_t kb = 1 << 20;
-    if (const char *e = getenv("DH_NW_CHUNK_KB")) kb = std::max<int64_t>(1, atoll(e));  // development
-    return kb * 128;
+    return dh_env_knob("DH_NW_CHUNK_KB", 1 << 20, 1, INT64_MAX) * 128;  // development; no upper bound
 }
 
 int64_t nwa_first_w()
 {
-    if (const char *e = getenv("DH_NWA_W0")) return std::min<int64_t>(std::max<int64_t>(1, atoll(e)), NWA_MAX_W);  // development
-    return 64;
+    return dh_env_knob("DH_NWA_W0", 64, 1, NWA_MAX_W);  // development
 }
 
 struct Job {
@@ -94,10 +85,10 @@ int run_launch(const NwaRun &r, const std::vector<Job> &jobs, size_t j0, size_t 
     NwPair *d_pairs;
     uint64_t *d_dm, *d_ow;
     EpResult *d_res;
-    if (int rc = scr(ctx, SLOT_NWA_PAIRS, n, &d_pairs)) return rc;
-    if (int rc = scr(ctx, SLOT_NWA_DM, (size_t)dm_words, &d_dm)) return rc;
-    if (int rc = scr(ctx, SLOT_NWA_OW, (size_t)ow_words, &d_ow)) return rc;
-    if (int rc = scr(ctx, SLOT_NWA_RES, n, &d_res)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_NWA_PAIRS, n, &d_pairs)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_NWA_DM, (size_t)dm_words, &d_dm)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_NWA_OW, (size_t)ow_words, &d_ow)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_NWA_RES, n, &d_res)) return rc;
     HIPCHK(hipMemcpyAsync(d_pairs, pairs.data(), sizeof(NwPair) * n, hipMemcpyHostToDevice, st));
     for (size_t a = 0, b; a < n; a = b) {  // one launch per class
         for (b = a + 1; b < n && jobs[j0 + b].cpl == jobs[j0 + a].cpl && jobs[j0 + b].ns == jobs[j0 + a].ns; b++) {}
@@ -128,8 +119,8 @@ int run_launch(const NwaRun &r, const std::vector<Job> &jobs, size_t j0, size_t 
     if (total == 0) return DH_OK;
     EpCopy *d_cp;
     uint8_t *d_out;
-    if (int rc = scr(ctx, SLOT_NWA_COPY, cp.size(), &d_cp)) return rc;
-    if (int rc = scr(ctx, SLOT_NWA_OPS, (size_t)total, &d_out)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_NWA_COPY, cp.size(), &d_cp)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_NWA_OPS, (size_t)total, &d_out)) return rc;
     HIPCHK(hipMemcpyAsync(d_cp, cp.data(), sizeof(EpCopy) * cp.size(), hipMemcpyHostToDevice, st));
     dhk_edit_compact(st, d_cp, (int32_t)cp.size(), nullptr, d_ow, d_out);
     HIPCHK(hipGetLastError());
@@ -158,8 +149,8 @@ int run_chunk(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off, const uin
     hipStream_t st = ctx->stream;
     const int64_t rbytes = ref_off[p1] - ref_off[p0], qbytes = qry_off[p1] - qry_off[p0];
     uint8_t *d_ref, *d_qry;
-    if (int rc = scr(ctx, SLOT_NWA_REF, (size_t)rbytes + 2 * NW_SEQ_PAD, &d_ref)) return rc;
-    if (int rc = scr(ctx, SLOT_NWA_QRY, (size_t)qbytes + 2 * NW_SEQ_PAD, &d_qry)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_NWA_REF, (size_t)rbytes + 2 * NW_SEQ_PAD, &d_ref)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_NWA_QRY, (size_t)qbytes + 2 * NW_SEQ_PAD, &d_qry)) return rc;
     if (rbytes) HIPCHK(hipMemcpyAsync(d_ref + NW_SEQ_PAD, ref + ref_off[p0], (size_t)rbytes, hipMemcpyHostToDevice, st));
     if (qbytes) HIPCHK(hipMemcpyAsync(d_qry + NW_SEQ_PAD, qry + qry_off[p0], (size_t)qbytes, hipMemcpyHostToDevice, st));
     const NwaRun r{ctx, ref_off, qry_off, p0, d_ref, d_qry, cost, &out, &stage};

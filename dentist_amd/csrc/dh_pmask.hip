@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "dh_pmask.h"
+#include "dh_scan.h"
 
 using pm::Raw;
 using pm::Rec;
@@ -49,14 +50,6 @@ k_pm_compact(const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ has,
     if (cnt[i0 + i]) list[has[i0 + i]] = i0 + i;
 }
 
-__device__ __forceinline__ int32_t wave_incl_scan(int32_t v, int32_t lane)
-{
-    for (int d = 1; d < 64; d <<= 1) {
-        const int32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
 __device__ __forceinline__ int64_t shfl64(int64_t v, int src)
 {
     const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, 64), hi = (uint32_t)__shfl((int)(uint32_t)((uint64_t)v >> 32), src, 64);

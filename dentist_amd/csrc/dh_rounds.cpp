@@ -21,7 +21,6 @@ void dhk_seg_vote(hipStream_t st, const void *segs, int32_t nseg, DbView T, DbVi
                   uint32_t *vother, int32_t *status, int32_t mode);
 void dhk_votes_finish(hipStream_t st, DbView T, const int64_t *voff, const int32_t *col_tmpl, int64_t ncols_total,
                       const uint32_t *cexcl, const uint32_t *vother, uint32_t *votes);
-void dhk_scan(hipStream_t st, uint32_t *v, int64_t n, uint32_t *sums);
 void dhk_col_tmpl(hipStream_t st, const int64_t *voff, int32_t ntmpl, int64_t ncols_total, int32_t *col_tmpl);
 void dhk_emit(hipStream_t st, DbView T, int32_t ntmpl, const int64_t *voff, const uint32_t *votes,
               const int32_t *col_tmpl, int64_t ncols_total, uint8_t *stage, uint8_t *cnt,

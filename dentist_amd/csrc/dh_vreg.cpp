@@ -8,15 +8,13 @@
 // DH_VREG_SLAB_MB.  Per group: the lists are written, the spanning records ordered, the regions' weak intervals counted, placed
 // by the host and emitted; intervals and spanning ids come back in one copy each.  The results are put in input order and the
 // mask is merged on the host.  DH_TRACE prints a line per call.
-#include "dh_internal.h"
+#include "dh_host.h"
 
 #include <stdio.h>
 #include <stdlib.h>
 
-#include <chrono>
 #include <memory>
 
-#include "dh_parallel.h"
 #include "dh_vreg.h"
 
 using vr::Job;
@@ -45,26 +43,6 @@ static_assert(sizeof(u64) == sizeof(uint64_t), "the counters are read as uint64_
 
 namespace {
 
-template <typename T>
-int scr(dh_ctx *ctx, DhSlot id, size_t count, T **out)
-{
-    return dh_scratch(ctx, id, sizeof(T) * std::max<size_t>(count, 1), (void **)out);
-}
-
-template <typename T>
-int upload(dh_ctx *ctx, DhSlot id, const T *v, size_t count, T **out)
-{
-    if (int rc = scr(ctx, id, count, out)) return rc;
-    if (count) HIPCHK(hipMemcpyAsync(*out, v, sizeof(T) * count, hipMemcpyHostToDevice, ctx->stream));
-    return DH_OK;
-}
-
-int64_t env_knob(const char *name, int64_t dflt, int64_t lo, int64_t hi)
-{
-    if (const char *e = getenv(name)) return std::min<int64_t>(std::max<int64_t>(lo, atoll(e)), hi);
-    return dflt;
-}
-
 int validate(dh_ctx *ctx, const char *fn, const dh_la *las, int64_t n, const int64_t *contig_off, int32_t ncontigs, const dh_region *regions,
              int32_t nregions, int32_t region_context, int32_t window, int32_t min_cov, int32_t min_span, dh_region_result **out)
 {
@@ -76,13 +54,13 @@ int validate(dh_ctx *ctx, const char *fn, const dh_la *las, int64_t n, const int
     const auto t_call = std::chrono::steady_clock::now();
     // 8192 entries = 32 KB of the 160 KB of a CU: five workgroups of 256 lanes per CU, and every region of up to 6 690 bases
     // (the default context and window) stays in LDS.  Above 16 000 a workgroup's array would not fit the 64 KB of a launch.
-    const int64_t lds_windows = env_knob("DH_VREG_LDS_WINDOWS", 8192, 2, 16000);  // development
-    const int64_t budget = env_knob("DH_VREG_SLAB_MB", 1024, 1, 65536) << 20;
+    const int64_t lds_windows = dh_env_knob("DH_VREG_LDS_WINDOWS", 8192, 2, 16000);  // development
+    const int64_t budget = dh_env_knob("DH_VREG_SLAB_MB", 1024, 1, 65536) << 20;
     // ---- the plan, before anything is launched
     vr::Plan pl;
     vr::Fault f;
     vr::build_plan(las, n, contig_off, ncontigs, regions, nregions, region_context, window,
-                   [](int64_t m, const std::function<void(int64_t, int64_t)> &body) { dh_parallel_for(m, 1 << 14, body); }, pl, f);
+                   dh_plan_runner<DH_PLAN_GRAIN>, pl, f);
     if (f.contig >= 0) return dh_fail(DH_EINVAL, name + ": contig " + std::to_string(f.contig) + ": " + f.what);
     if (f.record >= 0) return dh_fail(DH_EINVAL, name + ": record " + std::to_string(f.record) + ": " + f.what);
     if (f.region >= 0) return dh_fail(DH_EINVAL, name + ": region " + std::to_string(f.region) + ": " + f.what);
@@ -107,17 +85,17 @@ int validate(dh_ctx *ctx, const char *fn, const dh_la *las, int64_t n, const int
     Pair *d_pairs;
     int32_t *d_span_out, *d_slab, *d_iv;
     uint32_t *d_rcnt;
-    if (int rc = upload(ctx, SLOT_VR_RECS, pl.recs.data(), (size_t)n, &d_recs)) return rc;
-    if (int rc = upload(ctx, SLOT_VR_REGS, pl.regs.data(), nreg, &d_regs)) return rc;
-    if (int rc = upload(ctx, SLOT_VR_RPTR, pl.rptr.data(), pl.rptr.size(), &d_rptr)) return rc;
-    if (int rc = scr(ctx, SLOT_VR_CNT, 3 * nreg, &d_cnt)) return rc;
+    if (int rc = dh_upload(ctx, SLOT_VR_RECS, pl.recs.data(), (size_t)n, &d_recs)) return rc;
+    if (int rc = dh_upload(ctx, SLOT_VR_REGS, pl.regs.data(), nreg, &d_regs)) return rc;
+    if (int rc = dh_upload(ctx, SLOT_VR_RPTR, pl.rptr.data(), pl.rptr.size(), &d_rptr)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_VR_CNT, 3 * nreg, &d_cnt)) return rc;
     HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(u64) * 3 * nreg, st));
     dhk_vr_bind(st, 0, d_recs, 0, n, d_rptr, d_regs, 0, (int64_t)nreg, d_cnt, nullptr, nullptr, nullptr, nullptr);
     HIPCHK(hipGetLastError());
     std::vector<uint64_t> cnt(3 * nreg);
     HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(uint64_t) * cnt.size(), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    const double ms_count = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    const double ms_count = dh_ms_since(t_call);
     for (size_t s = 0; s < nreg; s++) {
         res->pairs += (int64_t)cnt[3 * s];
         res->big_regions += vr::is_big(vr::live_windows(pl.regs[s], cnt[3 * s]), lds_windows) ? 1 : 0;
@@ -160,14 +138,14 @@ int validate(dh_ctx *ctx, const char *fn, const dh_la *las, int64_t n, const int
             }
             if (!big) nsmall = (int64_t)jobs.size();
         }
-        if (int rc = upload(ctx, SLOT_VR_AT, at.data(), at.size(), &d_at)) return rc;
-        if (int rc = upload(ctx, SLOT_VR_JOBS, jobs.data(), jobs.size(), &d_jobs)) return rc;
-        if (int rc = scr(ctx, SLOT_VR_CUR, 2 * ng, &d_cur)) return rc;
-        if (int rc = scr(ctx, SLOT_VR_PAIRS, (size_t)npairs, &d_pairs)) return rc;
-        if (int rc = scr(ctx, SLOT_VR_SPAN_IDX, (size_t)nspan, &d_span_idx)) return rc;
-        if (int rc = scr(ctx, SLOT_VR_SPAN_OUT, (size_t)nspan, &d_span_out)) return rc;
-        if (int rc = scr(ctx, SLOT_VR_SLAB, (size_t)nslab, &d_slab)) return rc;
-        if (int rc = scr(ctx, SLOT_VR_RCNT, 2 * ng, &d_rcnt)) return rc;
+        if (int rc = dh_upload(ctx, SLOT_VR_AT, at.data(), at.size(), &d_at)) return rc;
+        if (int rc = dh_upload(ctx, SLOT_VR_JOBS, jobs.data(), jobs.size(), &d_jobs)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_VR_CUR, 2 * ng, &d_cur)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_VR_PAIRS, (size_t)npairs, &d_pairs)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_VR_SPAN_IDX, (size_t)nspan, &d_span_idx)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_VR_SPAN_OUT, (size_t)nspan, &d_span_out)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_VR_SLAB, (size_t)nslab, &d_slab)) return rc;
+        if (int rc = dh_scr(ctx, SLOT_VR_RCNT, 2 * ng, &d_rcnt)) return rc;
         HIPCHK(hipMemsetAsync(d_cur, 0, sizeof(u64) * 2 * ng, st));
         if (npairs + nspan > 0) {
             // the records of the group's contigs (the records are sorted by aread)
@@ -191,8 +169,8 @@ int validate(dh_ctx *ctx, const char *fn, const dh_la *las, int64_t n, const int
             niv += (int64_t)rcnt[2 * q];
         }
         if (niv > 0) {
-            if (int rc = upload(ctx, SLOT_VR_JOBS, jobs.data(), jobs.size(), &d_jobs)) return rc;
-            if (int rc = scr(ctx, SLOT_VR_IV, (size_t)(2 * niv), &d_iv)) return rc;
+            if (int rc = dh_upload(ctx, SLOT_VR_JOBS, jobs.data(), jobs.size(), &d_jobs)) return rc;
+            if (int rc = dh_scr(ctx, SLOT_VR_IV, (size_t)(2 * niv), &d_iv)) return rc;
             dhk_vr_region(st, 1, d_jobs, nsmall, (int64_t)ng, lds_entries, d_pairs, d_slab, min_cov, d_rcnt, d_iv);
             HIPCHK(hipGetLastError());
             iv.resize((size_t)(2 * niv));
@@ -228,7 +206,7 @@ int validate(dh_ctx *ctx, const char *fn, const dh_la *las, int64_t n, const int
                 "[vreg] %lld records, %d regions (%lld in the slab), %lld pairs, %zu launch groups; plan+upload+count %.2f ms, total %.2f ms; "
                 "%zu weak intervals, %zu spanning ids\n",
                 (long long)n, nregions, (long long)res->big_regions, (long long)res->pairs, groups.size(), ms_count,
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(), res->weak.size() / 3,
+                dh_ms_since(t_call), res->weak.size() / 3,
                 res->span_ids.size());
     *out = res.release();
     return DH_OK;
@@ -248,10 +226,11 @@ extern "C" int dh_la_set_validate_regions(dh_ctx *ctx, const dh_la_set *set, con
                                           const dh_region *regions, int32_t nregions, int32_t region_context, int32_t weak_coverage_window,
                                           int32_t min_coverage_reads, int32_t min_spanning_reads, dh_region_result **out)
 {
-    if (!ctx || !set) return dh_fail(DH_EINVAL, "dh_la_set_validate_regions: bad argument");
-    if (set->la.empty() && set->d_la_n > 0) return dh_fail(DH_EINVAL, "dh_la_set_validate_regions: the set's records are on the device only");
-    return validate(ctx, "dh_la_set_validate_regions", set->la.data(), (int64_t)set->la.size(), contig_off, ncontigs, regions, nregions,
-                    region_context, weak_coverage_window, min_coverage_reads, min_spanning_reads, out);
+    const dh_la *las;
+    int64_t n;
+    if (int rc = dh_set_host_records("dh_la_set_validate_regions", ctx != nullptr, set, &las, &n)) return rc;
+    return validate(ctx, "dh_la_set_validate_regions", las, n, contig_off, ncontigs, regions, nregions, region_context, weak_coverage_window,
+                    min_coverage_reads, min_spanning_reads, out);
 }
 
 extern "C" void dh_region_result_destroy(dh_region_result *r) { delete r; }

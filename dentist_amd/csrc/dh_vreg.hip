@@ -19,6 +19,7 @@
 
 #include <algorithm>
 
+#include "dh_scan.h"
 #include "dh_vreg.h"
 
 using vr::Job;
@@ -76,36 +77,6 @@ k_vr_span(const Rec *__restrict__ recs, const int64_t *__restrict__ at, const u6
     }
 }
 
-// the scan of one value per thread over the block: *excl = the values in front of the thread's, *total = all of them
-template <bool MAX>
-__device__ __forceinline__ int32_t vr_op(int32_t x, int32_t y)
-{
-    return MAX ? (x > y ? x : y) : x + y;
-}
-template <bool MAX>
-__device__ __forceinline__ void block_scan(int32_t v, int32_t *ws, int32_t *excl, int32_t *total)
-{
-    const int32_t ident = MAX ? -1 : 0;  // (the maxima are window starts or -1)
-    const int32_t lane = (int32_t)(threadIdx.x & 63), wave = (int32_t)(threadIdx.x >> 6);
-    for (int d = 1; d < 64; d <<= 1) {
-        const int32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v = vr_op<MAX>(v, t);
-    }
-    int32_t before = __shfl_up(v, 1, 64);
-    if (lane == 0) before = ident;
-    if (lane == 63) ws[wave] = v;
-    __syncthreads();
-    int32_t pre = ident, tot = ident;
-    for (int w = 0; w < VR_BLOCK / 64; w++) {
-        const int32_t x = ws[w];
-        if (w < wave) pre = vr_op<MAX>(pre, x);
-        tot = vr_op<MAX>(tot, x);
-    }
-    __syncthreads();  // (ws is written again by the next scan)
-    *excl = vr_op<MAX>(pre, before);
-    *total = tot;
-}
-
 // rcnt: 2 per job, the intervals of the region and their bases (EMIT: not written); iv: the group's intervals
 template <bool EMIT, bool BIG>
 __global__ void __launch_bounds__(VR_BLOCK)
@@ -141,15 +112,15 @@ k_vr_region(const Job *__restrict__ jobs, const Pair *__restrict__ pairs, int32_
         // (the slab was written by atomics, which are served by the L2: read it there)
         const int32_t d = !in ? 0 : (BIG ? __hip_atomic_load(diff + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : diff[w]);
         int32_t excl, total;
-        block_scan<false>(d, ws, &excl, &total);
+        block_scan<VR_BLOCK, ScanSum, 0>(d, ws, &excl, &total);
         const int32_t cov = cov_carry + excl + d;
         cov_carry += total;
         const bool weak = in && cov < min_cov;
-        block_scan<true>(weak ? (int32_t)w : -1, ws, &excl, &total);
+        block_scan<VR_BLOCK, ScanMax, -1>(weak ? (int32_t)w : -1, ws, &excl, &total);  // (the maxima are window starts or -1)
         const int32_t last = excl > last_carry ? excl : last_carry;
         last_carry = total > last_carry ? total : last_carry;
         const bool open = weak && vr::opens(w, last, j.wlen);
-        block_scan<false>(open ? 1 : 0, ws, &excl, &total);
+        block_scan<VR_BLOCK, ScanSum, 0>(open ? 1 : 0, ws, &excl, &total);
         const uint32_t rank = rank_carry + (uint32_t)excl;
         rank_carry += (uint32_t)total;
         if (open) {

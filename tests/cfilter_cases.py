@@ -273,6 +273,25 @@ def empty_reads_case():
     return case(rows, [10000], [6000] * 9)
 
 
+def scan_blocks_case(nreads=4200, block=2048):
+    """both device scans across their blocks of 2048 values: three blocks of per-record flags and of the nreads + 1 per-read
+    counts.  Most reads have one chain of one record (every 97th of low quality); reads at the front, around the first block
+    boundary and at the end have none; read block + 4 has a chain of two, whose records are block - 1 and block, and a unit
+    inside it on the same strand (Contained): its unit ids and its read offset need the carry of the block in front"""
+    empty = {0, 1, block - 1, block, block + 1, nreads - 2, nreads - 1}
+    rows = []
+    for r in range(nreads):
+        if r in empty:
+            continue
+        if r == block + 4:
+            assert sum(len(np.atleast_1d(x)) for x in rows) == block - 1
+            rows.append(chain_of(2, 0, r, 500, 1000))             # (the read sticks out of the contig: not redundant)
+            rows.append(la(0, r, 600, 1300, 1100, 1800, 10))
+            continue
+        rows.append(la(r & 1, r, 0, 3000, 1000, 4000, 1200 if r % 97 == 0 else 100, (r >> 1) & 1))
+    return case(rows, [100_000, 100_000], [4000] * nreads, opts=LOOSE)
+
+
 def all_disabled_case():
     c = planted_case()
     c["las"]["flags"] |= DISABLED
@@ -288,7 +307,7 @@ SHAPES = {
     "ambiguous_2": ambiguous_read(2), "ambiguous_64": ambiguous_read(64), "ambiguous_65": ambiguous_read(65),
     "chains": chains_case(), "boundaries": boundaries_case(), "many_intervals": many_intervals_case(), "contained": contained_case(),
     "planted": planted_case(), "empty_reads": empty_reads_case(), "all_disabled": all_disabled_case(),
-    "no_mask": dict(planted_case(), mask=None), "no_records": case([], [1000], [100, 100]),
+    "no_mask": dict(planted_case(), mask=None), "no_records": case([], [1000], [100, 100]), "scan_blocks": scan_blocks_case(),
 }
 SHAPES.update(RANDOM)
 # the tiers at their boundaries: name -> (reads of the wave tier, of the LDS tier, of the global tier) with the default cap and
