@@ -132,3 +132,12 @@ tests/native/libcfilt_host.so: tests/native/cfilt_host.cpp dentist_amd/csrc/dh_c
 # and the tier lists are where this code would overrun
 tests/native/cfilt_host_san: tests/native/cfilt_host_main.cpp tests/native/cfilt_host.cpp dentist_amd/csrc/dh_cfilt.h include/dentist_hip.h
 	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/cfilt_host_main.cpp tests/native/cfilt_host.cpp
+
+# the plan lane code of the chain padder (dentist_amd/csrc/dh_chainpad.h) compiled for the CPU: test infrastructure
+tests/native/libchainpad_host.so: tests/native/chainpad_host.cpp dentist_amd/csrc/dh_chainpad.h
+	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -o $@ $<
+
+# the same harness and a stand-alone main under the host sanitizers (a program of its own: nothing is preloaded); run it once
+# after a change to dh_chainpad.h -- the last trace value of a record and the last record of a chain are where this code would overrun
+tests/native/chainpad_host_san: tests/native/chainpad_host_main.cpp tests/native/chainpad_host.cpp dentist_amd/csrc/dh_chainpad.h
+	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/chainpad_host_main.cpp tests/native/chainpad_host.cpp

@@ -109,7 +109,7 @@ SYMBOLS = [
     "dh_la_edit_paths", "dh_la_set_edit_paths", "dh_edit_paths_destroy", "dh_edit_paths_count", "dh_edit_paths_op_off",
     "dh_edit_paths_ops", "dh_edit_paths_score", "dh_edit_paths_tile_off", "dh_edit_paths_tile_score",
     "dh_edit_paths_general_tiles", "dh_format_cigar", "dh_format_alignment", "dh_la_transpose", "dh_la_set_transpose",
-    "dh_nw_batch", "dh_nw_affine_batch", "dh_format_pair",
+    "dh_nw_batch", "dh_nw_affine_batch", "dh_format_pair", "dh_la_chain_paths", "dh_la_set_chain_paths", "dh_edit_paths_fillers", "dh_edit_paths_entry_fillers",
     "dh_exact_locate", "dh_exact_hits_destroy", "dh_exact_hits_count", "dh_exact_hits_records",
     "dh_default_chain_opts", "dh_la_chain", "dh_la_set_chain", "dh_la_chains_destroy", "dh_la_chains_count", "dh_la_chains_records",
     "dh_la_chains_off", "dh_la_chains_score", "dh_la_chains_src_index", "dh_la_chains_flags", "dh_la_chains_big_pairs",
@@ -236,11 +236,13 @@ def lib():
     L.dh_la_set_transpose.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     L.dh_edit_paths_destroy.argtypes = [vp]
     L.dh_edit_paths_destroy.restype = None
-    for fn in (L.dh_edit_paths_count, L.dh_edit_paths_general_tiles):
+    L.dh_la_chain_paths.argtypes = [vp, vp, vp, vp, i64, vp, i32, vp, i64, ctypes.POINTER(vp), vp]
+    L.dh_la_set_chain_paths.argtypes = [vp, vp, vp, vp, ctypes.POINTER(vp), vp]
+    for fn in (L.dh_edit_paths_count, L.dh_edit_paths_general_tiles, L.dh_edit_paths_fillers):
         fn.argtypes = [vp]
         fn.restype = i64
     for fn in (L.dh_edit_paths_op_off, L.dh_edit_paths_ops, L.dh_edit_paths_score, L.dh_edit_paths_tile_off,
-               L.dh_edit_paths_tile_score):
+               L.dh_edit_paths_tile_score, L.dh_edit_paths_entry_fillers):
         fn.argtypes = [vp]
         fn.restype = vp
     L.dh_format_cigar.argtypes = [vp, i64, i32, vp, i64]
@@ -493,6 +495,36 @@ class Context:
             _check(L.dh_la_edit_paths(self._h, A._h, B._h, arr.ctypes.data, len(arr), tr.ctypes.data, int(tspace), int(first),
                                       int(count), ctypes.byref(h)))
         return EditPaths(h)
+
+    def chain_paths(self, A, B, las, trace=None, tspace=None, chain_off=None):
+        """dh_la_chain_paths: the base-level alignment of whole chains (the chain padder).  chain_off: nchains + 1 record
+        offsets (what Chains gives together with chains_to_set), None = chains by flags (a record without NEXT starts one).
+        `las` may be a raw handle of align_db_block(..., raw=True) (dh_la_set_chain_paths, by flags).  Returns (op_off, ops,
+        score, status, fillers): status[i] is CP_OK, CP_FAKED or CP_NESTED (no ops, score -1), fillers the number of
+        fillers the global-alignment kernel aligned."""
+        h = ctypes.c_void_p()
+        L = lib()
+        if isinstance(las, ctypes.c_void_p):
+            if chain_off is not None:
+                raise ValueError("a set's chains are read from its flags")
+            status = np.zeros(max(int(L.dh_la_set_count(las)), 1), dtype=np.int32)
+            _check(L.dh_la_set_chain_paths(self._h, A._h, B._h, las, ctypes.byref(h), status.ctypes.data))
+        else:
+            arr = np.ascontiguousarray(las, dtype=LA_DTYPE)
+            tr = np.ascontiguousarray(trace, dtype=np.uint16)
+            status = np.zeros(max(len(arr), 1), dtype=np.int32)
+            co, nch = None, 0
+            if chain_off is not None:
+                co = np.ascontiguousarray(chain_off, dtype=np.int64)
+                if len(co) < 1:
+                    raise ValueError("chain_off needs nchains + 1 entries")
+                nch = len(co) - 1
+                status = np.zeros(max(nch, 1), dtype=np.int32)
+            _check(L.dh_la_chain_paths(self._h, A._h, B._h, arr.ctypes.data if len(arr) else None, len(arr),
+                                       tr.ctypes.data if len(tr) else None, int(tspace), None if co is None else co.ctypes.data, nch,
+                                       ctypes.byref(h), status.ctypes.data))
+        ep = EditPaths(h)
+        return ep.op_off.copy(), ep.ops.copy(), ep.score.copy(), status[:len(ep)].copy(), int(L.dh_edit_paths_fillers(ep._h))
 
     def nw_batch(self, refs, qrys, free_shift=False):
         """dh_nw_batch: the global alignment (findAlignment, indel penalty 1) of refs[i] against qrys[i] for every i; the
@@ -851,6 +883,7 @@ def format_cigar(ops, extended=True):
 
 
 NW_OK, NW_BAND_EXCEEDED = 0, 1
+CP_OK, CP_FAKED, CP_NESTED = 0, 1, 2  # status of Context.chain_paths
 NW_MAX_LEN, NW_MAX_BAND = 65536, 4096
 
 

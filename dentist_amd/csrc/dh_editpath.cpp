@@ -36,6 +36,11 @@ extern "C" const int32_t *dh_edit_paths_score(const dh_edit_paths *p) { return p
 extern "C" const int64_t *dh_edit_paths_tile_off(const dh_edit_paths *p) { return p ? p->tile_off.data() : nullptr; }
 extern "C" const uint16_t *dh_edit_paths_tile_score(const dh_edit_paths *p) { return p ? p->tile_score.data() : nullptr; }
 extern "C" int64_t dh_edit_paths_general_tiles(const dh_edit_paths *p) { return p ? p->general_tiles : 0; }
+extern "C" int64_t dh_edit_paths_fillers(const dh_edit_paths *p) { return p ? p->fillers : 0; }
+extern "C" const int32_t *dh_edit_paths_entry_fillers(const dh_edit_paths *p)
+{
+    return p && !p->entry_fillers.empty() ? p->entry_fillers.data() : nullptr;
+}
 
 namespace {
 
@@ -401,6 +406,20 @@ int transpose_impl(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la *las, int64_t n,
 }
 
 }  // namespace
+
+int dh_ep_check_record(const dh_db *A, const dh_db *B, const dh_la &la, int64_t idx, const uint16_t *trace, int64_t trace_len,
+                       int32_t ts, std::vector<EpTile> &tiles)
+{
+    return cut_record(A, B, la, idx, trace, trace_len, ts, tiles);
+}
+
+size_t dh_ep_chunk_tiles() { return edit_chunk(); }
+
+int dh_ep_run_tiles(dh_ctx *ctx, dh_db *A, dh_db *B, int32_t ts, const std::vector<EpTile> &tiles, size_t t0, size_t t1,
+                    std::vector<EpResult> &res, dh_edit_paths *out, const uint8_t **d_ops)
+{
+    return run_chunk(ChunkRun{ctx, A, B, ts}, tiles, t0, t1, res, out, d_ops);
+}
 
 extern "C" int dh_la_transpose(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la *las, int64_t n, const uint16_t *trace,
                                int32_t tspace, int32_t want_best, dh_la_set **out, int64_t *src_index)

@@ -148,6 +148,14 @@ enum DhSlot : int {
     SLOT_CF_RECS, SLOT_CF_ALEN, SLOT_CF_BLEN, SLOT_CF_MASK_PTR, SLOT_CF_MASK_IV, SLOT_CF_MASK_PRE, SLOT_CF_FLAG, SLOT_CF_UID, SLOT_CF_SUMS,
     SLOT_CF_FIRST, SLOT_CF_UNITS, SLOT_CF_WHY, SLOT_CF_CNT, SLOT_CF_CUR, SLOT_CF_GIDX, SLOT_CF_USED, SLOT_CF_OUT, SLOT_CF_CTR, SLOT_CF_CNT6,
     SLOT_CF_LWAVE, SLOT_CF_LLDS, SLOT_CF_LGLOB, SLOT_CF_SLAB_AT, SLOT_CF_SLAB,
+    // chain padder (dh_la_chain_paths, dh_chainpad.cpp): all live for one launch group of chains.  The compact records, their trace
+    // values and the chains' record ranges are the input; SLOT_CP_NSEG / NTILE / NFILL are per chain (counts, then their scans),
+    // SLOT_CP_STATUS per chain, SLOT_CP_SEGS / TILES / FILLS what the plan writes; SLOT_CP_TILE_OP the first op of every tile in
+    // SLOT_EP_OPS, SLOT_CP_FILL_SRC / FILL_NOPS / FILL_OPS the fillers' ops; SLOT_CP_LEN per chain (length, then its scan),
+    // SLOT_CP_OUT / SCORE the stitched ops and scores, SLOT_CP_SUMS / TOTAL the scans' block sums and totals
+    SLOT_CP_RECS, SLOT_CP_TRACE, SLOT_CP_CHAIN_OFF, SLOT_CP_NSEG, SLOT_CP_NTILE, SLOT_CP_NFILL, SLOT_CP_STATUS, SLOT_CP_SEGS,
+    SLOT_CP_TILES, SLOT_CP_FILLS, SLOT_CP_TILE_OP, SLOT_CP_FILL_SRC, SLOT_CP_FILL_NOPS, SLOT_CP_FILL_OPS, SLOT_CP_LEN, SLOT_CP_OUT,
+    SLOT_CP_SCORE, SLOT_CP_SUMS, SLOT_CP_TOTAL,
     DH_SLOT_COUNT
 };
 // The words of SLOT_STATUS (DH_STW_COUNT x int32), one buffer with three users.  All of them run on the context's stream:
@@ -392,7 +400,31 @@ struct dh_edit_paths {
     std::vector<int32_t> score;
     std::vector<uint16_t> tile_score;
     int64_t general_tiles = 0;
+    int64_t fillers = 0;                 // dh_la_chain_paths: fillers the global-alignment kernel aligned ...
+    std::vector<int32_t> entry_fillers;  // ... and how many of them every chain has (empty for the other calls)
 };
+
+// dh_nw.cpp: the widening protocol of the global alignment on pairs whose sequences are on the device (dh_nw_batch's chunks, the
+// chain padder's fillers)
+struct DhNwSeq {
+    int64_t roff, qoff;  // first base in the device reference / query bytes
+    int32_t rl, ql;
+};
+struct DhNwPairOut {
+    int64_t at = 0;  // first op in the staging vector
+    int32_t nops = 0, score = 0, status = 0;  // status: DH_NW_OK / DH_NW_BAND_EXCEEDED
+};
+int dh_nw_run_pairs(dh_ctx *ctx, const uint8_t *d_ref, const uint8_t *d_qry, const DhNwSeq *seq, const std::vector<int64_t> &todo,
+                    int32_t fs, std::vector<DhNwPairOut> &out, std::vector<uint8_t> &stage);
+// dh_editpath.cpp: validation of one record as dh_la_edit_paths validates it (its tiles are appended to `tiles`), and the tiles [t0, t1) of `tiles` through the edit-path kernels with their
+// ops left on the device, tile after tile (*d_ops; NULL when there is none): res[t] = nops / score per tile
+struct EpTile;
+struct EpResult;
+int dh_ep_check_record(const dh_db *A, const dh_db *B, const dh_la &la, int64_t idx, const uint16_t *trace, int64_t trace_len,
+                       int32_t ts, std::vector<EpTile> &tiles);
+size_t dh_ep_chunk_tiles();  // DH_EDIT_CHUNK
+int dh_ep_run_tiles(dh_ctx *ctx, dh_db *A, dh_db *B, int32_t ts, const std::vector<EpTile> &tiles, size_t t0, size_t t1,
+                    std::vector<EpResult> &res, dh_edit_paths *out, const uint8_t **d_ops);
 
 // dh_pileups.cpp: LA indices shifted by a constant; pile-ups of several parts concatenated gap by gap
 void dh_pileups_shift(dh_pileups *p, int32_t by);

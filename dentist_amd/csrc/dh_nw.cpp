@@ -42,15 +42,11 @@ struct Job {
     int64_t words;  // decision words
 };
 
-struct PairOut {
-    int64_t at = 0;  // first op in the staging vector
-    int32_t nops = 0, score = 0, status = DH_NW_OK;
-};
+using PairOut = DhNwPairOut;
 
 struct NwRun {
     dh_ctx *ctx;
-    const int64_t *ref_off, *qry_off;
-    int64_t p0;  // first pair of the chunk: its sequences start at NW_SEQ_PAD of the device buffers
+    const DhNwSeq *seq;  // by pair of the call: where its sequences are in the device buffers
     const uint8_t *d_ref, *d_qry;
     int32_t fs;
     std::vector<PairOut> *out;
@@ -67,11 +63,12 @@ int run_launch(const NwRun &r, const std::vector<Job> &jobs, size_t j0, size_t j
     int64_t dm_words = 0, ow_words = 0;
     for (size_t k = 0; k < n; k++) {
         const Job &jb = jobs[j0 + k];
+        const DhNwSeq &sq = r.seq[jb.pair];
         NwPair &p = pairs[k];
-        p.roff = NW_SEQ_PAD + r.ref_off[jb.pair] - r.ref_off[r.p0];
-        p.qoff = NW_SEQ_PAD + r.qry_off[jb.pair] - r.qry_off[r.p0];
-        p.rl = (int32_t)(r.ref_off[jb.pair + 1] - r.ref_off[jb.pair]);
-        p.ql = (int32_t)(r.qry_off[jb.pair + 1] - r.qry_off[jb.pair]);
+        p.roff = sq.roff;
+        p.qoff = sq.qoff;
+        p.rl = sq.rl;
+        p.ql = sq.ql;
         p.lo = jb.b.lo;
         p.hi = jb.b.hi;
         p.dm_off = dm_words;
@@ -129,9 +126,10 @@ int run_launch(const NwRun &r, const std::vector<Job> &jobs, size_t j0, size_t j
     return DH_OK;
 }
 
-// the device pairs `todo` of chunk [p0, p1): attempts at growing half-widths until every pair is accepted or given up
+// the pairs `todo` of the chunk [p0, p1) of a call on host sequences: their bases go to the device once
 int run_chunk(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off, const uint8_t *qry, const int64_t *qry_off, int64_t p0,
-              int64_t p1, const std::vector<int64_t> &todo, int32_t fs, std::vector<PairOut> &out, std::vector<uint8_t> &stage)
+              int64_t p1, const std::vector<int64_t> &todo, int32_t fs, std::vector<DhNwSeq> &seq, std::vector<PairOut> &out,
+              std::vector<uint8_t> &stage)
 {
     hipStream_t st = ctx->stream;
     const int64_t rbytes = ref_off[p1] - ref_off[p0], qbytes = qry_off[p1] - qry_off[p0];
@@ -140,7 +138,21 @@ int run_chunk(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off, const uin
     if (int rc = dh_scr(ctx, SLOT_NW_QRY, (size_t)qbytes + 2 * NW_SEQ_PAD, &d_qry)) return rc;
     if (rbytes) HIPCHK(hipMemcpyAsync(d_ref + NW_SEQ_PAD, ref + ref_off[p0], (size_t)rbytes, hipMemcpyHostToDevice, st));
     if (qbytes) HIPCHK(hipMemcpyAsync(d_qry + NW_SEQ_PAD, qry + qry_off[p0], (size_t)qbytes, hipMemcpyHostToDevice, st));
-    const NwRun r{ctx, ref_off, qry_off, p0, d_ref, d_qry, fs, &out, &stage};
+    for (int64_t p : todo)
+        seq[(size_t)p] = DhNwSeq{NW_SEQ_PAD + ref_off[p] - ref_off[p0], NW_SEQ_PAD + qry_off[p] - qry_off[p0],
+                                 (int32_t)(ref_off[p + 1] - ref_off[p]), (int32_t)(qry_off[p + 1] - qry_off[p])};
+    return dh_nw_run_pairs(ctx, d_ref, d_qry, seq.data(), todo, fs, out, stage);
+}
+
+}  // namespace
+
+// The widening protocol, shared by dh_nw_batch and the chain padder's fillers (dh_chainpad.cpp): attempts at growing
+// half-widths until every pair of `todo` is accepted or given up.  The sequences are on the device already, NW_SEQ_PAD
+// readable bytes on either side of each; seq is indexed by pair, as out is.
+int dh_nw_run_pairs(dh_ctx *ctx, const uint8_t *d_ref, const uint8_t *d_qry, const DhNwSeq *seq, const std::vector<int64_t> &todo,
+                    int32_t fs, std::vector<DhNwPairOut> &out, std::vector<uint8_t> &stage)
+{
+    const NwRun r{ctx, seq, d_ref, d_qry, fs, &out, &stage};
     const int64_t budget = nw_budget_words(), w0 = nw_first_w();
     std::vector<Job> jobs, again;
     for (int64_t p : todo) {
@@ -152,7 +164,7 @@ int run_chunk(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off, const uin
     while (!again.empty()) {
         jobs.clear();
         for (Job jb : again) {
-            const int32_t rl = (int32_t)(ref_off[jb.pair + 1] - ref_off[jb.pair]), ql = (int32_t)(qry_off[jb.pair + 1] - qry_off[jb.pair]);
+            const int32_t rl = seq[jb.pair].rl, ql = seq[jb.pair].ql;
             jb.w = nw::next_w(rl, ql, fs, jb.w, w0);
             if (jb.w < 0) {
                 PairOut &o = out[(size_t)jb.pair];
@@ -178,8 +190,6 @@ int run_chunk(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off, const uin
     return DH_OK;
 }
 
-}  // namespace
-
 extern "C" int dh_nw_batch(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off, const uint8_t *qry, const int64_t *qry_off,
                            int64_t n, int32_t free_shift, dh_edit_paths **out, int32_t *status)
 {
@@ -204,6 +214,7 @@ extern "C" int dh_nw_batch(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_o
     if (n > 0 && ((ref_off[n] > ref_off[0] && !ref) || (qry_off[n] > qry_off[0] && !qry)))
         return dh_fail(DH_EINVAL, "dh_nw_batch: sequences are NULL");
     std::vector<PairOut> po((size_t)n);
+    std::vector<DhNwSeq> seq((size_t)n);
     std::vector<uint8_t> stage;
     // ---- chunks of consecutive pairs: the decision words of the first attempts within the budget, 256 MB of bases at most
     const int64_t budget = nw_budget_words(), w0 = nw_first_w();
@@ -232,7 +243,7 @@ extern "C" int dh_nw_batch(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_o
             HIPCHK(hipSetDevice(ctx->device));
             device_set = true;
         }
-        if (int rc = run_chunk(ctx, ref, ref_off, qry, qry_off, p0, p1, todo, fs, po, stage)) return rc;
+        if (int rc = run_chunk(ctx, ref, ref_off, qry, qry_off, p0, p1, todo, fs, seq, po, stage)) return rc;
     }
     // ---- the result in pair order; a pair with an empty side is all insertions or all deletions (oracle/nw.c)
     std::unique_ptr<dh_edit_paths> p(new dh_edit_paths);

@@ -723,6 +723,49 @@ int64_t dh_format_cigar(const uint8_t *ops, int64_t nops, int32_t extended, char
 int64_t dh_format_alignment(const uint8_t *a, const uint8_t *b, const uint8_t *ops, int64_t nops, int32_t width,
                             char *out, int64_t cap);
 
+/* ---- base-level alignment of whole chains: AlignmentPadder (dazzler.d:2249-2607) over every chain from the start of its
+ *      first record to the end of its last.  A chain is the records [chain_off[i], chain_off[i + 1]) (what dh_la_chains_off
+ *      and dh_la_chains_to_set produce), or, with chain_off == NULL (nchains is ignored then), read from the flags: a record
+ *      without DH_FLAG_NEXT starts a chain and every following DH_FLAG_NEXT record continues it.  The records of a chain
+ *      share aread, bread and DH_FLAG_COMP and do not decrease in abpos; DH_FLAG_DISABLED is ignored.
+ *      Per chain one op string in dh_la_edit_paths' codes (COMP chains in the reverse-complement frame of B) that consumes
+ *      exactly A [abpos of the first record, aepos of the last) and B [bbpos of the first, bepos of the last).  It is the
+ *      concatenation of tile runs (a contiguous range of a record's trace tiles, their ops exactly dh_la_edit_paths') and of
+ *      fillers between a record p and the next record q: dh_nw_batch's free-shift alignment of an A range against a B range.
+ *      Trace points: a record's begin, its tile ends and its end; floor = the last one at or before a position, ceil = the
+ *      first one at or behind it, on A or on the trace's running B sum.
+ *        gap (p.aepos <= q.abpos and p.bepos <= q.bbpos): p keeps its remaining tiles, the filler is A [p.aepos, q.abpos) x
+ *          B [p.bepos, q.bbpos), q starts at its first tile; a filler without bases is no segment.
+ *        overlap (getNonOverlappingCoordinates, :2512-2560): on every sequence X that overlaps, begin = p's floor point of
+ *          q.Xbpos and end = q's ceil point of p.Xepos; of two the begin with the smaller A and the end with the larger A.  p's
+ *          tile run ends at begin, q's starts at end, the filler is A [begin.A, end.A) x B [begin.B, end.B).
+ *      status (one entry per chain -- n entries always suffice -- or NULL); the call succeeds in every case:
+ *        DH_CP_OK
+ *        DH_CP_FAKED   a filler came back DH_NW_BAND_EXCEEDED or exceeds DH_NW_MAX_LEN and was written as the reference's
+ *                      "faking too long alignment gap" (:2450-2474): |la - lb| indels (insertions if A is the shorter side),
+ *                      then min(la, lb) columns, each 0 or 3 by comparing the bases
+ *        DH_CP_NESTED  a junction whose begin lies before the point where p's own tile run starts, or whose end lies before
+ *                      its begin on A or on B.  The chain has no ops and score -1.
+ *      Deviation: cleanUpLocalAlignments (findTilings, :2354-2394) is not restated -- dh_la_chain's max_relative_overlap
+ *      keeps nested records out of its chains, and what still arrives is reported as DH_CP_NESTED, not guessed.
+ *      out: a dh_edit_paths of one entry per chain (dh_edit_paths_count; every accessor and both formatters apply): op_off /
+ *      ops, score[i] = its number of non-zero ops, tile_off all zero, general_tiles as for dh_la_edit_paths;
+ *      dh_edit_paths_fillers = the fillers the global-alignment kernel aligned (0 for results of the other calls),
+ *      dh_edit_paths_entry_fillers = how many of them every chain has (one value per chain; NULL for the other calls).
+ *      DH_EINVAL, found on the host before anything is launched: whatever dh_la_edit_paths refuses; chain_off not starting
+ *      at 0, decreasing or ending past n; an empty chain; a chain whose records differ in aread / bread / COMP or decrease in
+ *      abpos (dh_last_error names the record).  No chains is no error and launches nothing. */
+#define DH_CP_OK 0
+#define DH_CP_FAKED 1
+#define DH_CP_NESTED 2
+int dh_la_chain_paths(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la *las, int64_t n, const uint16_t *trace,
+                      int32_t tspace, const int64_t *chain_off /* nchains + 1, or NULL: by flags */, int64_t nchains,
+                      dh_edit_paths **out, int32_t *status /* per chain, or NULL */);
+int dh_la_set_chain_paths(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_la_set *set, dh_edit_paths **out,
+                          int32_t *status); /* by flags */
+int64_t dh_edit_paths_fillers(const dh_edit_paths *p);
+const int32_t *dh_edit_paths_entry_fillers(const dh_edit_paths *p);
+
 /* ---- exact transposition of local alignments: the records `damapper -C` writes as <B>.<A>.las (dazzler.d:6158-6170,
  *      getLasFile :4339-4354) for alignments that already exist -- the SAME alignments with the roles of the sequences
  *      exchanged, not a second alignment of the transposed pair (dh_align_db_transposed).  Per record, from the ops of

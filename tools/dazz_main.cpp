@@ -21,7 +21,7 @@
 //                                    DB's track (snakemake/Snakefile:1111-1123; track layout dazzler.d:4943-5170)
 //   TANmask [-v] [-l<int(500)>] [-n<track(tan)>] <db> <TAN las>...   self alignments of a read -> mask intervals
 //                                    (snakemake/Snakefile:1095-1108); the block's track when the .las names a block
-//   LApaf [-a] [-w<int(100)>] <A:db|dam> [<B:db|dam>] <align:las> [first-last]   base-level alignments of the records of a
+//   LApaf [-a] [-c] [-w<int(100)>] <A:db|dam> [<B:db|dam>] <align:las> [first-last]   base-level alignments of the records of a
 //                                    .las as PAF with an extended cigar (dh_la_edit_paths: getExactAlignment's per-trace-point
 //                                    part, dazzler.d:2405-2426); -a adds the alignment text (SequenceAlignment.toString)
 //   LAtranspose [-b] <A:db|dam> <B:db|dam> <in:las> <out:las>   the same alignments with the roles of the sequences exchanged
@@ -759,6 +759,10 @@ static int tool_merge_insertions(const std::vector<std::string> &args)
 // complement records), the target the A sequence; names are the first word of the FASTA header (DAM) or the prolog (DB)
 // followed by /<1-based read number>.  Tags: NM:i the exact edit distance summed over the trace tiles, tp:i the sum of the
 // trace's diffs (what the aligner's band found), cg:Z the extended cigar (= X I D).
+// -c: one line per CHAIN of the file (a record without the NEXT flag starts a chain, file order), from dh_la_chain_paths: the
+// query range is the chain's B range, the target range its A range; NM:i the non-zero ops, nl:i the records of the chain, nf:i
+// the fillers aligned between them, cg:Z the cigar of the whole chain; fk:i:1 on a chain with a faked filler; a nested chain
+// prints 0 matches, * for the cigar and st:Z:nested.  first-last counts chains then.
 static std::string paf_name(const dh_dazz *d, int32_t i)
 {
     const char *h = dh_dazz_header(d, i);
@@ -772,12 +776,14 @@ static std::string paf_name(const dh_dazz *d, int32_t i)
 
 static int tool_lapaf(const std::vector<std::string> &args)
 {
-    bool show = false;
+    bool show = false, chains = false;
     int width = 100;
     std::vector<std::string> pos;
     for (const std::string &a : args) {
         if (a == "-a")
             show = true;
+        else if (a == "-c")
+            chains = true;
         else if (a.compare(0, 2, "-w") == 0)
             width = atoi(a.c_str() + 2);
         else if (a[0] == '-')
@@ -793,7 +799,7 @@ static int tool_lapaf(const std::vector<std::string> &args)
         }
         pos.pop_back();
     }
-    if (pos.size() < 2 || pos.size() > 3 || width < 1) die("usage: LApaf [-a] [-w<int(100)>] <A:db|dam> [<B:db|dam>] <align:las> [first-last]");
+    if (pos.size() < 2 || pos.size() > 3 || width < 1) die("usage: LApaf [-a] [-c] [-w<int(100)>] <A:db|dam> [<B:db|dam>] <align:las> [first-last]");
     const bool two = pos.size() == 3 && pos[1] != pos[0];
     Dev va = open_dev(pos[0]);
     Dev vb;
@@ -811,24 +817,48 @@ static int tool_lapaf(const std::vector<std::string> &args)
         l.aread -= dh_dazz_first_id(da);
         l.bread -= dh_dazz_first_id(dbz);
     }
-    if (r1 < 0) r1 = n;
-    if (r0 < 1 || r1 > n || r0 > r1 + 1) die("record range outside the file (" + std::to_string(n) + " records)");
+    // the entries of the output: records, or (-c) chains by flags as record ranges
+    std::vector<int64_t> coff;
+    if (chains) {
+        for (int64_t i = 0; i < n; i++)
+            if (i == 0 || !(las[(size_t)i].flags & DH_FLAG_NEXT)) coff.push_back(i);
+        coff.push_back(n);
+    }
+    const int64_t nent = chains ? (int64_t)coff.size() - 1 : n;
+    if (r1 < 0) r1 = nent;
+    if (r0 < 1 || r1 > nent || r0 > r1 + 1)
+        die(std::string(chains ? "chain" : "record") + " range outside the file (" + std::to_string(nent) + (chains ? " chains)" : " records)"));
     const uint16_t *trace = dh_la_set_trace(set);
     const int32_t ts = dh_la_set_tspace(set);
     dh_edit_paths *ep = nullptr;
-    CHK(dh_la_edit_paths(va.ctx, A, B, las.data(), n, trace, ts, r0 - 1, r1 - r0 + 1, &ep));
+    std::vector<int32_t> cstatus;
+    if (chains) {
+        const int64_t cnt = r1 - r0 + 1, rec0 = coff[(size_t)(r0 - 1)];
+        std::vector<int64_t> off((size_t)cnt + 1);
+        for (int64_t k = 0; k <= cnt; k++) off[(size_t)k] = coff[(size_t)(r0 - 1 + k)] - rec0;
+        cstatus.assign((size_t)cnt + 1, 0);
+        CHK(dh_la_chain_paths(va.ctx, A, B, las.data() + rec0, n - rec0, trace, ts, off.data(), cnt, &ep, cstatus.data()));
+    } else {
+        CHK(dh_la_edit_paths(va.ctx, A, B, las.data(), n, trace, ts, r0 - 1, r1 - r0 + 1, &ep));
+    }
     const int64_t *op_off = dh_edit_paths_op_off(ep);
     const uint8_t *ops = dh_edit_paths_ops(ep);
     const int32_t *score = dh_edit_paths_score(ep);
+    const int32_t *nfill = dh_edit_paths_entry_fillers(ep);
     const int64_t *aoff = dh_dazz_offsets(da), *boff = dh_dazz_offsets(dbz);
     std::vector<char> text;
     std::vector<uint8_t> brc;
     for (int64_t i = 0; i < dh_edit_paths_count(ep); i++) {
-        const dh_la &l = las[(size_t)(r0 - 1 + i)];
+        // the entry as one record: a chain from the begin of its first record to the end of its last
+        const int64_t f = chains ? coff[(size_t)(r0 - 1 + i)] : r0 - 1 + i, e = chains ? coff[(size_t)(r0 + i)] : f + 1;
+        dh_la l = las[(size_t)f];
+        l.aepos = las[(size_t)(e - 1)].aepos;
+        l.bepos = las[(size_t)(e - 1)].bepos;
         const uint8_t *o = ops + op_off[i];
         const int64_t no = op_off[i + 1] - op_off[i];
         const int64_t alen = aoff[l.aread + 1] - aoff[l.aread], blen = boff[l.bread + 1] - boff[l.bread];
         const bool comp = (l.flags & DH_FLAG_COMP) != 0;
+        const bool nested = chains && cstatus[(size_t)i] == DH_CP_NESTED;
         int64_t nmatch = 0, tdiffs = 0;
         for (int64_t k = 0; k < no; k++) nmatch += o[k] == 0;
         for (int32_t t = 0; t < l.tlen; t += 2) tdiffs += trace[l.toff + t];
@@ -836,11 +866,18 @@ static int tool_lapaf(const std::vector<std::string> &args)
         if (clen < 0) die(dh_last_error());
         text.resize((size_t)clen + 1);
         dh_format_cigar(o, no, 1, text.data(), clen + 1);
-        printf("%s\t%lld\t%lld\t%lld\t%c\t%s\t%lld\t%d\t%d\t%lld\t%lld\t255\tNM:i:%d\ttp:i:%lld\tcg:Z:%s\n", paf_name(dbz, l.bread).c_str(),
-               (long long)blen, (long long)(comp ? blen - l.bepos : l.bbpos), (long long)(comp ? blen - l.bbpos : l.bepos),
-               comp ? '-' : '+', paf_name(da, l.aread).c_str(), (long long)alen, l.abpos, l.aepos, (long long)nmatch, (long long)no,
-               score[i], (long long)tdiffs, text.data());
-        if (!show) continue;
+        printf("%s\t%lld\t%lld\t%lld\t%c\t%s\t%lld\t%d\t%d\t%lld\t%lld\t255\tNM:i:%d", paf_name(dbz, l.bread).c_str(), (long long)blen,
+               (long long)(comp ? blen - l.bepos : l.bbpos), (long long)(comp ? blen - l.bbpos : l.bepos), comp ? '-' : '+',
+               paf_name(da, l.aread).c_str(), (long long)alen, l.abpos, l.aepos, (long long)nmatch, (long long)no, score[i]);
+        if (!chains) {
+            printf("\ttp:i:%lld\tcg:Z:%s\n", (long long)tdiffs, text.data());
+        } else {
+            printf("\tnl:i:%lld\tnf:i:%d\tcg:Z:%s", (long long)(e - f), nfill ? nfill[i] : 0, nested ? "*" : text.data());
+            if (cstatus[(size_t)i] == DH_CP_FAKED) printf("\tfk:i:1");
+            if (nested) printf("\tst:Z:nested");
+            putchar('\n');
+        }
+        if (!show || nested) continue;
         const uint8_t *a = dh_dazz_bases(da) + aoff[l.aread] + l.abpos, *b = dh_dazz_bases(dbz) + boff[l.bread] + l.bbpos;
         if (comp) {  // the B side of the record in the reverse-complement frame
             brc.resize((size_t)(l.bepos - l.bbpos));
