@@ -1018,10 +1018,17 @@ static int seed_chunk(AlignRun &r, AlignChunk &c, bool *redo)
         while (capj < tier_max && 1.5 * mean_hits > capj) capj *= 2;
         if (wave_tier) capj = 512;
     }
+    // (an unsampled mapping -- 925 hits per 15 kb read, 1.5 x the mean above 512 -- takes the middle tier: 2048 hits, four
+    // wavefronts per read and 64 candidate band pairs, five blocks per CU where the 512-thread block keeps three.  A read
+    // with more hits or more band pairs is marked like an overflow of the wavefront tier and redone from the list by the
+    // 512-thread tiers; the context stops using the tier once a quarter of a chunk's reads were.  A block gathers one
+    // segment per thread.  DH_SEED_NO_MID_TIER=1: the 512-thread block as before)
+    const bool mid_tier = (mj_chunk || tj_chunk) && !wave_tier && capj == 2048 && ctx->seed_mid_tier &&
+                          (!mj_chunk || c.mv.nseg <= 256) && !getenv("DH_SEED_NO_MID_TIER");
     if (jn && capj > 4096) SCR(SLOT_FSCR, d_fscr, (size_t)ctx->ncu * DH_SEED_FSCR_BLOCKS_PER_CU * (capj > 8192 ? DH_SEED_FSCR_WORDS16 : DH_SEED_FSCR_WORDS))
     if (jn)
         dhk_seed_join(st, capj, r.bv, r.iv, r.dopt, jvx, (int32_t)item0, ni, c.candbase, c.ncandbase, c.nhitsbase, r.d_status,
-                      r.d_queue + 1, ctx->ncu, d_fscr, nullptr, 0);
+                      r.d_queue + 1, ctx->ncu, d_fscr, nullptr, 0, mid_tier ? 1 : 0);
     else
         dhk_seed(st, r.cap, r.bv, r.iv, r.dopt, (int32_t)item0, ni, c.candbase, c.ncandbase, c.nhitsbase, r.d_status,
                  r.d_queue + 1, ctx->ncu, d_fscr);
@@ -1095,13 +1102,23 @@ static int seed_chunk(AlignRun &r, AlignChunk &c, bool *redo)
     if (mj_chunk) ctx->mj_chunks++;
     if (tj_chunk) ctx->tj_last_hits += (int64_t)tj_hits;
     r.mj_skip_chunk = false;  // (the next chunk tries the join again)
-    if (jn && capj < tier_max && !big.empty()) {
+    if (mid_tier) {
+        ctx->seed_mid_chunks++;
+        ctx->seed_mid_redone += (int64_t)big.size();
+        if (big.size() * 4 > (size_t)(ni / 2)) ctx->seed_mid_tier = 0;
+        if (getenv("DH_TRACE"))
+            fprintf(stderr, "[seeds] middle tier (256 threads, 2048 hits, 64 band pairs): %d reads, %zu redone by the 512-thread tiers%s\n",
+                    ni / 2, big.size(), ctx->seed_mid_tier ? "" : ": not used by this context any more");
+    }
+    // (the middle tier's reads with too many band pairs have at most 2048 hits: the tiers below start at 2048 again)
+    const int held = mid_tier ? 0 : capj;
+    if (jn && held < tier_max && !big.empty()) {
         // further tiers of the join path: the reads above the first capacity that fit the 8192-entry variant, then the
         // 16384-entry one (uncapped pile-ups: ~10 000 hits per read); what is left is staged in HBM
         std::vector<int32_t> huge;
         int32_t gcap2 = 0;
-        for (int tier = capj < 2048 ? 2048 : 8192; tier <= tier_max; tier = tier < 8192 ? 8192 : tier * 2) {
-            if (tier <= capj) continue;
+        for (int tier = held < 2048 ? 2048 : 8192; tier <= tier_max; tier = tier < 8192 ? 8192 : tier * 2) {
+            if (tier <= held) continue;
             std::vector<int32_t> mid;
             huge.clear();
             gcap2 = 0;
@@ -1123,7 +1140,7 @@ static int seed_chunk(AlignRun &r, AlignChunk &c, bool *redo)
                 HIPCHK(hipMemcpyAsync(d_mid, mid.data(), sizeof(int32_t) * mid.size(), hipMemcpyHostToDevice, st));
                 HIPCHK(hipMemsetAsync(r.d_queue + 1, 0, sizeof(uint32_t), st));
                 dhk_seed_join(st, tier, r.bv, r.iv, r.dopt, jvx, (int32_t)item0, ni, c.candbase, c.ncandbase, c.nhitsbase, r.d_status,
-                              r.d_queue + 1, ctx->ncu, d_fscr2, d_mid, (int32_t)mid.size());
+                              r.d_queue + 1, ctx->ncu, d_fscr2, d_mid, (int32_t)mid.size(), 0);
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipStreamSynchronize(st));  // mid goes out of scope
             }

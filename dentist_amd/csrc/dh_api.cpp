@@ -159,6 +159,15 @@ extern "C" int dh_get_tjoin_counts(dh_ctx *c, int64_t *out4, int32_t reset)
     return DH_OK;
 }
 
+extern "C" int dh_get_seed_tier_counts(dh_ctx *c, int64_t *out2, int32_t reset)
+{
+    if (!c || !out2) return fail(DH_EINVAL, "dh_get_seed_tier_counts: NULL");
+    out2[0] = c->seed_mid_chunks;
+    out2[1] = c->seed_mid_redone;
+    if (reset) c->seed_mid_chunks = c->seed_mid_redone = 0;
+    return DH_OK;
+}
+
 extern "C" int dh_get_join_counts(dh_ctx *c, int64_t *out4, int32_t reset)
 {
     if (!c || !out4) return fail(DH_EINVAL, "dh_get_join_counts: NULL");

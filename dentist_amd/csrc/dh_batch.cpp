@@ -277,6 +277,10 @@ void fold_part_counters(dh_ctx *ctx, int32_t nparts)
         ctx->tj_last_hits += sc->tj_last_hits;
         ctx->tj_reruns += sc->tj_reruns;
         sc->tj_calls = sc->tj_fallbacks = sc->tj_last_hits = sc->tj_reruns = 0;
+        // ... and the middle seed tier of those rounds (dh_get_seed_tier_counts)
+        ctx->seed_mid_chunks += sc->seed_mid_chunks;
+        ctx->seed_mid_redone += sc->seed_mid_redone;
+        sc->seed_mid_chunks = sc->seed_mid_redone = 0;
     }
 }
 

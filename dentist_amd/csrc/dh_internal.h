@@ -200,6 +200,10 @@ struct dh_ctx {
     dh_cum_stats cum = {};
     double mj_hit_frac = 0.2;  // hits per sampled k-mer the hit pool of the partitioned join is sized for (raised when a pool overflowed)
     int seed_wave_tier = 1;  // the wavefront-per-read first tier of the segment-fed seed back end (0: most reads overflowed it)
+    // the middle tier of that back end (256 threads, 2048 hits, 64 band pairs per read; 0: a quarter of a chunk's reads
+    // overflowed it) and dh_get_seed_tier_counts' two counters: chunks whose first tier it was, reads redone behind it
+    int seed_mid_tier = 1;
+    int64_t seed_mid_chunks = 0, seed_mid_redone = 0;
     int64_t mj_chunks = 0, mj_fallbacks = 0;  // chunks seeded by the partitioned join / redone by the directory (dh_get_mjoin_counts)
     // the per-group table join (dh_tjoin.h; dh_get_tjoin_counts): calls seeded by it, grouped calls A != B that kept the
     // directory because a limit was not met, hits of the last call, reruns of the hit buffer -- and the hits per base of B

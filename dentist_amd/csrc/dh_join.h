@@ -76,10 +76,11 @@ void dhk_join_part(hipStream_t st, JoinView jv, DbView B, int32_t k, int32_t kme
 void dhk_join(hipStream_t st, JoinView jv, DbView B, DhOpts o, const int64_t *goff, int32_t sepv);
 /* reads with more than 2048 / 4096 / 8192 hits and the largest hit count of a read */
 void dhk_join_hist(hipStream_t st, JoinView jv, const int32_t *group, int32_t nreads, unsigned int *out4);
-/* the seed filter's back end fed from the join's hit segments (cap: LDS hit capacity as in dhk_seed) */
+/* the seed filter's back end fed from the join's hit segments (cap: LDS hit capacity as in dhk_seed; mid_tier with a cap of
+   2048: the 256-thread block with 64 candidate band pairs, whose reads with more are marked like those with too many hits) */
 void dhk_seed_join(hipStream_t st, int cap, DbView B, IndexView ix, DhOpts o, JoinView jv, int32_t item0, int32_t nitems,
                    DhCand *cand, int32_t *ncand, int32_t *nhits, int32_t *status, uint32_t *queue, int32_t ncu,
-                   uint64_t *fscr, const int32_t *read_list, int32_t nlist);
+                   uint64_t *fscr, const int32_t *read_list, int32_t nlist, int32_t mid_tier);
 void dhk_seed_big_join(hipStream_t st, DbView B, IndexView ix, DhOpts o, JoinView jv, const int32_t *read_list,
                        int32_t nreads, uint64_t *gbuf, int32_t gcap, DhCand *cand, int32_t *ncand, int32_t *nhits,
                        int32_t *status, uint32_t *queue, int32_t ncu);

@@ -8,6 +8,8 @@
 //     band pairs  coverage of neighbouring diagonal bands, local maxima become candidates with a seed
 //     rank, write candidates ranked per strand, the best max_cand written
 //   LCAP > 0: hits staged in LDS; LCAP == 0: in a slab of HBM (reads that overflowed every LDS tier).
+//   Segment-fed tiers below the 512-thread blocks: <512, 64, 32> a wavefront per read (sampled mapping), <2048, 256, 64>
+//   four wavefronts per read with a slim LDS layout (unsampled mapping).
 // k_seed_summary  per-chunk sums of the per-item results
 // dhk_seed, dhk_seed_big, dhk_seed_join, dhk_seed_big_join: tier tables over launch_seed
 //
@@ -56,7 +58,14 @@ __device__ __forceinline__ int32_t hit_cov(const uint64_t *h, int32_t i, int32_t
 // (gcap entries per block, items taken from item_list) -- same code, same results.
 #ifdef DH_SEED_PROF
 __device__ unsigned long long g_seed_prof[12];
-#define SP(i) if (tid == 0) { const unsigned long long t_ = wall_clock64(); atomicAdd(&g_seed_prof[i], t_ - tp_); tp_ = t_; }
+// (a block's clocks add up in LDS and reach g_seed_prof when the persistent block ends: as ten atomics per read on one
+// cache line -- 10^7 per mapping launch at ~10 ns each -- the instrumentation was what the instrumented kernel waited for)
+__device__ __forceinline__ unsigned long long *seed_prof_lds()
+{
+    __shared__ unsigned long long s_prof[12];
+    return s_prof;
+}
+#define SP(i) if (tid == 0) { const unsigned long long t_ = wall_clock64(); seed_prof_lds()[i] += t_ - tp_; tp_ = t_; }
 #else
 #define SP(i)
 #endif
@@ -77,9 +86,22 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
                           int32_t *__restrict__ nhits_out, int32_t *__restrict__ status,
                           uint64_t *__restrict__ gbuf, int32_t gcap, const int32_t *__restrict__ read_list)
 {
+    // Which sort a tier takes goes by (LCAP, NT), not by the block size alone:
+    //   RANK_ALL  one wavefront whose lanes rank each of their keys against all n hits (n x LCAP / NT compares: for the 512
+    //             hits of the wavefront-per-read tier only)
+    //   otherwise one hit per thread (n <= NT), the diagonal buckets, or the bitonic network
+    // SLIM (the middle tier: four wavefronts per read, 2 048 hits, CC = 64): the segment tables of the gather and the
+    // counters of the bucket sort overlay the prefix sums and band heads of the band phase (not live before the hits are
+    // sorted) instead of the candidate arrays, which therefore need not hold 8 + 4 KB: 31.5 KB of LDS per block, five
+    // blocks per CU where the 512-thread block of the same capacity keeps three.
+    constexpr bool RANK_ALL = LCAP > 0 && NT <= LANES && LCAP <= 8 * NT;
+    constexpr bool SLIM = LCAP > 0 && LCAP <= 4096 && NT > LANES && NT < SEED_THREADS;
+    constexpr bool FB_LDS = LCAP > 0 && LCAP <= 4096;  // the band phase's prefix sums and heads live in LDS
     __shared__ uint64_t lhits[LCAP > 0 ? LCAP : 1];
     __shared__ DhCand cands[2 * CC];
     __shared__ int64_t cband[2 * CC];
+    __shared__ __attribute__((aligned(8))) uint32_t bsum_l[FB_LDS ? LCAP : 1];   // inclusive prefix sums
+    __shared__ __attribute__((aligned(8))) uint16_t bhead_l[FB_LDS ? LCAP : 1];  // positions of the band heads
     __shared__ int32_t s_n, s_nc;
 
     const int32_t r = read_list ? read_list[work] : read0 + work;  // (the HBM variant always works from a list)
@@ -115,9 +137,13 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
     // of rolling threads makes it 40 % slower), so every thread of the block takes a chunk.
     if (JOIN) {
         // the read's segments: one per slice of its group (segtab row), first hit << 24 | count.  Their prefix sums
-        // and first hits overlay the candidate arrays, which are not in use yet.
-        uint64_t *segb = (uint64_t *)cands;                     // [NT] first hit of segment s
-        uint32_t *sego = (uint32_t *)(cands + CC) + 1;   // [-1 .. NT) exclusive prefix sums of the counts
+        // and first hits overlay the candidate arrays, which are not in use yet (SLIM: the band phase's arrays).
+        static_assert(SLIM || (sizeof(cands) / 2 >= NT * sizeof(uint64_t) && sizeof(cands) / 2 >= (NT + 1) * sizeof(uint32_t)),
+                      "segment tables overlay the candidate array");
+        static_assert(!SLIM || (sizeof(bsum_l) >= NT * sizeof(uint64_t) && sizeof(bhead_l) >= (NT + 1) * sizeof(uint32_t)),
+                      "segment tables overlay the band arrays");
+        uint64_t *segb = SLIM ? (uint64_t *)bsum_l : (uint64_t *)cands;                        // [NT] first hit of segment s
+        uint32_t *sego = (SLIM ? (uint32_t *)bhead_l : (uint32_t *)(cands + CC)) + 1;   // [-1 .. NT) exclusive prefix sums of the counts
         __shared__ uint32_t s_jw[NT / LANES];
         const int32_t ns = jv.gns ? jv.gns[B.group[r]] : jv.ns_fixed;
         const int64_t srow = jv.gns ? jv.segrow[r] : (int64_t)(r - jv.read0) * jv.ns_fixed;
@@ -348,8 +374,7 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
     // ---- sort of the hit buffer (keys are distinct: a hit is (strand, diagonal, read position))
     int32_t N = 1;
     while (N < n) N <<= 1;
-    constexpr bool SMALL = NT < SEED_THREADS;  // a wavefront per read (the mapping launches' first tier): LCAP <= 8 NT
-    if (SMALL) {
+    if (RANK_ALL) {  // a wavefront per read (the sampled mapping's first tier)
         // every thread takes the (at most LCAP / NT) keys tid, tid + NT, ... and counts the keys below each of them: n
         // broadcast reads for all of its keys together; keys are distinct, the ranks a permutation
         // (as many keys per thread as the read needs: 140 hits at 1/8 sampling are three)
@@ -411,8 +436,10 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
         constexpr int E = LCAP >= NT ? LCAP / NT : 1;
         constexpr int NB = 2048, NBH = NB / 2, SORT_BMAX = LCAP == 0 ? 384 : 256;
         constexpr uint64_t DM = (1ull << HIT_DBITS) - 1;
-        static_assert(SMALL || sizeof(cands) >= NB * sizeof(uint32_t), "bucket counters overlay the candidate array");
-        uint32_t *bcnt = (uint32_t *)cands;  // not in use yet (the join's segment table is done with it)
+        static_assert(NB % NT == 0 && NT % LANES == 0, "every thread scans NB / NT counters, whole wavefronts");
+        static_assert(RANK_ALL || SLIM || sizeof(cands) >= NB * sizeof(uint32_t), "bucket counters overlay the candidate array");
+        static_assert(!SLIM || sizeof(bsum_l) >= NB * sizeof(uint32_t), "bucket counters overlay the prefix sums");
+        uint32_t *bcnt = SLIM ? (uint32_t *)bsum_l : (uint32_t *)cands;  // not in use yet (the join's segment table is done with it)
         __shared__ unsigned long long s_dmin, s_dmax;
         __shared__ uint32_t s_bw[NT / LANES];
         __shared__ uint32_t s_bmax;
@@ -422,9 +449,11 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
         // diagonal range over the whole assembly, so the slices are 10^5 diagonals wide and one of them holds everything --
         // 88 % of the reads of configs[2] took the network, 25.6 of the 41 us a block spent per read.
         constexpr int HV = 8, NB2 = 1024;            // heavy buckets a read may have; slices of the second pass
-        constexpr bool REFINE = LCAP > 0 && !SMALL;
-        static_assert(!REFINE || sizeof(cband) >= NB2 * sizeof(uint32_t), "the second pass's counters overlay the band array");
-        uint32_t *fcnt = (uint32_t *)cband;          // not in use yet
+        constexpr bool REFINE = LCAP > 0 && !RANK_ALL;
+        static_assert(!REFINE || SLIM || sizeof(cband) >= NB2 * sizeof(uint32_t), "the second pass's counters overlay the band array");
+        static_assert(!SLIM || sizeof(bhead_l) >= NB2 * sizeof(uint32_t), "the second pass's counters overlay the band heads");
+        static_assert(NB2 % NT == 0 && (LCAP == 0 || LCAP % NT == 0 || LCAP < NT), "NB2 / NT counters, LCAP / NT hits per thread");
+        uint32_t *fcnt = SLIM ? (uint32_t *)bhead_l : (uint32_t *)cband;  // not in use yet
         __shared__ uint32_t s_nheavy, s_heavy[HV];
         for (int32_t i = tid; i < NB; i += NT) bcnt[i] = 0;
         if (tid == 0) {
@@ -689,7 +718,7 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
             N = 1;
         } else {
 #ifdef DH_SEED_PROF
-            if (tid == 0) atomicAdd(&g_seed_prof[10], 1ull);
+            if (tid == 0) seed_prof_lds()[10] += 1ull;
 #endif
             for (int32_t i = n + tid; i < N; i += NT) hits[i] = ~0ull;
         }
@@ -770,21 +799,18 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
     // (the 16384-entry variant fed from segments -- uncapped pile-ups: 166 reads, ~10 000 hits per read -- scans as well,
     // with the wide sums of the HBM variant in a slab of 24 576 words per block; the directory-fed one keeps the walks)
     constexpr bool FASTB = LCAP <= 8192 || (JOIN && LCAP == 16384);
-    constexpr bool FB_LDS = LCAP > 0 && LCAP <= 4096;
     constexpr bool FB_BIG = LCAP == 0;
     constexpr bool FB_WIDE = LCAP == 0 || LCAP == 16384;
     using bsum_t = typename std::conditional<FB_WIDE, uint64_t, uint32_t>::type;
     using bhead_t = typename std::conditional<FB_WIDE, uint32_t, uint16_t>::type;
     constexpr int HSH = FB_WIDE ? 32 : 18;
     constexpr bsum_t CMASK = ((bsum_t)1 << HSH) - 1;
-    __shared__ uint32_t bsum_l[FB_LDS ? LCAP : 1];   // inclusive prefix sums
-    __shared__ uint16_t bhead_l[FB_LDS ? LCAP : 1];  // positions of the band heads
     bsum_t *bsum = FB_LDS ? (bsum_t *)bsum_l
                           : (FB_BIG ? (bsum_t *)(hits + gcap) : (bsum_t *)(gbuf + (int64_t)slab * gcap));
     bhead_t *bhead = FB_LDS ? (bhead_t *)bhead_l : (bhead_t *)(bsum + (LCAP > 0 ? LCAP : gcap));
     __shared__ bsum_t s_wsum[NT / LANES];
     __shared__ int32_t s_nbig;
-    constexpr int NBIG = NT < SEED_THREADS ? 8 : ((LCAP > 0 && LCAP <= 4096) ? 128 : 64);  // (the 8192-entry variant has no LDS to spare; what does not fit walks serially)
+    constexpr int NBIG = NT <= LANES ? 8 : (SLIM ? 16 : ((LCAP > 0 && LCAP <= 4096) ? 128 : 64));  // (the 8192-entry variant has no LDS to spare; what does not fit walks serially)
     __shared__ int32_t bigc[NBIG][4];  // candidate band pairs with long hit ranges: (first, end, P, slot)
     __shared__ unsigned long long s_bestkeys[NBIG];
     const int bs = o.band_shift;
@@ -898,7 +924,10 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
         // (a run = hits of one diagonal at most k apart) is the running maximum of the run heads' positions -- a scan
         // over the 16 lanes plus the carry of the lanes before --, not a walk back from every run end: the walks were a
         // chain of dependent LDS round trips as long as the longest run of the wavefront (13 of the 97 us per read)
-        constexpr int GW = 16;
+        // (SLIM: a wavefront per candidate -- an unsampled mapping read has two or three candidates whose band pairs hold
+        // most of its ~900 hits: at 16 lanes the walk was 56 dependent rounds by one quarter of a wavefront, 9.4 of the
+        // 31 us a 512-thread block spent per read, while every other lane waited at the barrier below; 3.7 us this way)
+        constexpr int GW = SLIM ? LANES : 16;
         const int32_t nbig = min(s_nbig, NBIG);
         const int gl = tid & (GW - 1);
         for (int32_t bc = tid / GW; bc < nbig; bc += NT / GW) {
@@ -962,10 +991,11 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
     if (nc > 2 * CC) {
         // more candidate band pairs than one read can sensibly have (a repeat the -t cap did not
         // catch): the read yields no alignments and is reported (ncand = -2), the launch goes on
-        // (the wavefront-per-read tier holds fewer: the read goes to the next tier, where the rule above decides)
+        // (the wavefront-per-read tier and the middle tier hold fewer: the read goes to a tier with the full SEED_CCAP,
+        // where the rule above decides)
         if (tid == 0) {
-            ncand_out[item] = ncand_out[item + 1] = NT < SEED_THREADS ? -1 : -2;
-            if (NT < SEED_THREADS) {
+            ncand_out[item] = ncand_out[item + 1] = CC < SEED_CCAP ? -1 : -2;
+            if (CC < SEED_CCAP) {
                 nhits_out[item] = n;
                 nhits_out[item + 1] = 0;
             }
@@ -1020,13 +1050,13 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
     if (tid < 2) ncand_out[item + tid] = s_ncs[tid] < o.max_cand ? s_ncs[tid] : o.max_cand;
     SP(4)
 #ifdef DH_SEED_PROF
-    if (tid == 0) atomicAdd(&g_seed_prof[7], 1ull);
+    if (tid == 0) seed_prof_lds()[7] += 1ull;
 #endif
 }
 // Persistent blocks: the grid is sized to the resident capacity of the chip and every block pulls
 // items from an atomic queue (no per-item block launch, dynamic balance over ragged read lengths).
 template <int LCAP, bool JOIN, int NT = SEED_THREADS, int CC = SEED_CCAP>
-__global__ void __launch_bounds__(NT, NT < SEED_THREADS ? 4 : ((LCAP > 0 && LCAP <= 2048) ? 6 : (LCAP == 16384 ? 2 : 4)))
+__global__ void __launch_bounds__(NT, NT <= LANES ? 4 : (NT < SEED_THREADS ? 5 : ((LCAP > 0 && LCAP <= 2048) ? 6 : (LCAP == 16384 ? 2 : 4))))
 k_seed(DbView B, IndexView ix, JoinView jv, DhOpts o, int32_t read0,
        int32_t nreads, DhCand *__restrict__ cand_out, int32_t *__restrict__ ncand_out,
        int32_t *__restrict__ nhits_out, int32_t *__restrict__ status, uint64_t *__restrict__ gbuf,
@@ -1037,6 +1067,10 @@ k_seed(DbView B, IndexView ix, JoinView jv, DhOpts o, int32_t read0,
     // each whatever the kernel did in between -- 5.7 of the wavefront-per-read tier's 5.7 ms, SQ_WAIT_ANY 88 %.  The small
     // tiers of the segment-fed back end take eight reads per atomic.)
     constexpr int32_t BATCH = (JOIN && LCAP > 0 && LCAP <= 2048) ? 8 : 1;
+#ifdef DH_SEED_PROF
+    if (threadIdx.x == 0)
+        for (int i = 0; i < 12; i++) seed_prof_lds()[i] = 0;
+#endif
     for (;;) {
         __syncthreads();  // the previous read is finished by every thread (shared state is reused)
         if (threadIdx.x == 0) s_work = (int32_t)atomicAdd(queue, (uint32_t)BATCH);
@@ -1052,6 +1086,11 @@ k_seed(DbView B, IndexView ix, JoinView jv, DhOpts o, int32_t read0,
                                           status, gbuf, gcap, read_list);
         }
     }
+#ifdef DH_SEED_PROF
+    if (threadIdx.x == 0)
+        for (int i = 0; i < 12; i++)
+            if (seed_prof_lds()[i]) atomicAdd(&g_seed_prof[i], seed_prof_lds()[i]);
+#endif
 }
 #define SEED_INST(C, J)                                                                           \
     template __global__ void k_seed<C, J>(DbView, IndexView, JoinView, DhOpts, int32_t, int32_t,  \
@@ -1066,6 +1105,8 @@ SEED_INST(0, false)
 SEED_INST(2048, true)
 template __global__ void k_seed<512, true, 64, 32>(DbView, IndexView, JoinView, DhOpts, int32_t, int32_t, DhCand *, int32_t *, int32_t *,
                                                    int32_t *, uint64_t *, int32_t, const int32_t *, uint32_t *);
+template __global__ void k_seed<2048, true, 256, 64>(DbView, IndexView, JoinView, DhOpts, int32_t, int32_t, DhCand *, int32_t *, int32_t *,
+                                                     int32_t *, uint64_t *, int32_t, const int32_t *, uint32_t *);
 SEED_INST(4096, true)
 SEED_INST(8192, true)
 SEED_INST(16384, true)
@@ -1083,6 +1124,8 @@ static int seed_grid(int32_t nitems, int32_t ncu)
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_seed<C, J, NT, CC>, NT, 0) != hipSuccess || nb < 1)
             nb = 1;
         per_cu = nb;
+        if (getenv("DH_TRACE"))
+            fprintf(stderr, "[seeds] k_seed<%d, %s, %d, %d>: %d resident blocks per CU\n", C, J ? "true" : "false", NT, CC, nb);
     }
     int use = per_cu;
     if (const char *e = getenv("DH_SEED_BLOCKS_PER_CU")) use = std::max(1, std::min(per_cu, atoi(e)));  // development
@@ -1159,7 +1202,8 @@ extern "C" void dhk_seed_big(hipStream_t st, DbView B, IndexView ix, DhOpts o,
 // the same back end fed from the hit segments of the per-pile-up k-mer join (dh_join.hip)
 extern "C" void dhk_seed_join(hipStream_t st, int cap, DbView B, IndexView ix, DhOpts o, JoinView jv, int32_t item0,
                               int32_t nitems, DhCand *cand, int32_t *ncand, int32_t *nhits, int32_t *status,
-                              uint32_t *queue, int32_t ncu, uint64_t *fscr, const int32_t *read_list, int32_t nlist)
+                              uint32_t *queue, int32_t ncu, uint64_t *fscr, const int32_t *read_list, int32_t nlist,
+                              int32_t mid_tier)
 {
     if (nitems <= 0 || (read_list && nlist <= 0)) return;
     seed_sort_switch();
@@ -1169,6 +1213,8 @@ extern "C" void dhk_seed_join(hipStream_t st, int cap, DbView B, IndexView ix, D
                           nhits,  status, read_list, queue, ncu};
     if (cap <= 512)  // the first tier of a mapping: a wavefront per read (140 hits at 1/8 sampling), 32 candidate band pairs
         launch_seed<512, true, 64, 32>(a, nullptr, 0);
+    else if (cap <= 2048 && mid_tier)  // an unsampled mapping (~900 hits per read): four wavefronts per read, 64 band pairs
+        launch_seed<2048, true, 256, 64>(a, nullptr, 0);
     else if (cap <= 2048)
         launch_seed<2048, true>(a, nullptr, 0);
     else if (cap <= 4096)
@@ -1193,7 +1239,11 @@ extern "C" void dhk_seed_prof_dump()
 {
     unsigned long long h[12];
     (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_seed_prof), sizeof(h));
-    fprintf(stderr, "[seed prof] blocks %llu: lookup %.1f sort %.1f bcov %.1f bands %.1f rank %.1f us/block (of the sort: buckets %.1f scatter %.1f; of the bands: heads %.1f long ranges %.1f; %llu reads through the network)\n", h[7], h[0] / 100.0 / h[7], h[1] / 100.0 / h[7], h[2] / 100.0 / h[7], h[3] / 100.0 / h[7], h[4] / 100.0 / h[7], h[5] / 100.0 / h[7], h[6] / 100.0 / h[7], h[8] / 100.0 / h[7], h[9] / 100.0 / h[7], h[10]);
+    // (a clock runs from the one before it: the sort is buckets + scatter + ranks, the bands are heads + long ranges + emit)
+    const double per = h[7] ? 1.0 / 100.0 / (double)h[7] : 0.0;
+    fprintf(stderr, "[seed prof] reads %llu: fill %.1f sort %.1f (buckets %.1f scatter %.1f ranks %.1f) bcov %.1f bands %.1f (heads %.1f long ranges %.1f emit %.1f) rank %.1f us/read; %llu reads through the network\n",
+            h[7], h[0] * per, (h[5] + h[6] + h[1]) * per, h[5] * per, h[6] * per, h[1] * per, h[2] * per, (h[8] + h[9] + h[3]) * per,
+            h[8] * per, h[9] * per, h[3] * per, h[4] * per, h[10]);
     unsigned long long z[12] = {0};
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_seed_prof), z, sizeof(z));
 }

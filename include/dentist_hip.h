@@ -171,6 +171,12 @@ int dh_get_join_counts(dh_ctx *ctx, int64_t *out4, int32_t reset);
  * the hit buffer.  After dh_process_pileups the counters of its concurrent parts are added to the context's.  Both paths
  * give the same alignments.  reset clears all four. */
 int dh_get_tjoin_counts(dh_ctx *ctx, int64_t *out4, int32_t reset);
+/* The middle tier of the segment-fed seed back end (256 threads, 2048 hits and 64 candidate band pairs per read: the first
+ * tier of a chunk of the mapping join or the table join whose reads have 342 to 1365 hits on average): out2[0] chunks whose
+ * first tier it was, out2[1] reads it could not hold (more hits or more band pairs), redone by the 512-thread tiers.  After
+ * dh_process_pileups the counters of its concurrent parts are added to the context's.  Every tier gives the same
+ * candidates.  reset clears both. */
+int dh_get_seed_tier_counts(dh_ctx *ctx, int64_t *out2, int32_t reset);
 /* The capacity (hits) that join's first attempt asks for -- host arithmetic only, no device needed.  bases[g] / reads[g]:
  * bases and reads of group g; rate: hits per base per read of depth (<= 0: the initial figure of a fresh context);
  * free_bytes: device memory free at that moment (< 0: not known, no clamp).  See dh_join_hit_capacity in csrc/dh_join.h. */
