@@ -68,6 +68,9 @@ INSERTION_DTYPE = np.dtype([(n, "<i4") for n in (
 EXACT_HIT_DTYPE = np.dtype([("query", "<i4"), ("ref", "<i4"), ("begin", "<i8"), ("end", "<i8"), ("complement", "<i4"),
                             ("pad", "<i4")])
 
+# dh_seed_cand (16 bytes): one candidate of the seed stage
+SEED_CAND_DTYPE = np.dtype([("score", "<i4"), ("aseq", "<i4"), ("apos", "<i4"), ("bpos", "<i4")])
+
 LA_DTYPE = np.dtype([("tlen", "<i4"), ("diffs", "<i4"), ("abpos", "<i4"), ("bbpos", "<i4"),
                      ("aepos", "<i4"), ("bepos", "<i4"), ("flags", "<u4"), ("aread", "<i4"),
                      ("bread", "<i4"), ("pad", "<i4"), ("toff", "<i8")])
@@ -79,7 +82,7 @@ SYMBOLS = [
     "dh_db_total_bases", "dh_la_set_destroy", "dh_la_set_count", "dh_la_set_trace_len",
     "dh_la_set_records", "dh_la_set_trace", "dh_la_set_tspace", "dh_get_align_stats", "dh_get_cum_stats", "dh_get_mjoin_counts", "dh_get_join_counts", "dh_get_tjoin_counts", "dh_get_seed_tier_counts", "dh_join_hit_capacity",
     "dh_ctx_release_scratch",
-    "dh_align_db",
+    "dh_align_db", "dh_seed_candidates",
     "dh_las_write", "dh_las_read", "dh_default_process_opts", "dh_collect_spanning", "dh_pileups_destroy",
     "dh_pileups_count", "dh_pileups_get", "dh_process_pileups", "dh_insertions_destroy",
     "dh_insertions_count", "dh_insertions_records", "dh_insertions_bases", "dh_insertions_bases_len",
@@ -164,6 +167,7 @@ def lib():
     L.dh_get_align_stats.argtypes = [vp, ctypes.POINTER(AlignStats)]
     L.dh_get_cum_stats.argtypes = [vp, ctypes.POINTER(CumStats), i32]
     L.dh_align_db.argtypes = [vp, vp, vp, ctypes.POINTER(AlignOpts), i32, ctypes.POINTER(vp)]
+    L.dh_seed_candidates.argtypes = [vp, vp, vp, ctypes.POINTER(AlignOpts), vp, vp, vp]
     L.dh_align_db_block.argtypes = [vp, vp, vp, i32, i32, ctypes.POINTER(AlignOpts), i32, ctypes.POINTER(vp)]
     L.dh_la_set_merge.argtypes = [ctypes.POINTER(vp), i32, ctypes.POINTER(vp)]
     L.dh_las_write.argtypes = [ctypes.c_char_p, vp, i64, vp, i32]
@@ -476,6 +480,16 @@ class Context:
         las, trace, _ = _take_la_set(h)
         return las, trace
 
+    def seed_candidates(self, A, B, opts):
+        """dh_seed_candidates: the seed stage of align_db alone.  Returns (cand[nitems, max_cand] SEED_CAND_DTYPE, ncand[nitems],
+        nhits[nitems]), item = 2 * read + strand; row i holds the ncand[i] candidates of item i in the order the extension
+        takes them (what lies behind them is not defined)."""
+        n = 2 * int(lib().dh_db_nreads(B._h))
+        cand = np.zeros((n, int(opts.max_cand)), dtype=SEED_CAND_DTYPE)
+        ncand, nhits = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        _check(lib().dh_seed_candidates(self._h, A._h, B._h, ctypes.byref(opts), cand.ctypes.data, ncand.ctypes.data,
+                                        nhits.ctypes.data))
+        return cand, ncand, nhits
 
     def map_reads(self, A, B, opts, popts, first=0, count=None, repeat_mask=None, sorted=True, candidates=False,
                   trace_on_device=False):

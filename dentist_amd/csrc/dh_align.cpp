@@ -39,9 +39,14 @@ extern "C" int dh_align_db(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_align_opts 
 // whole reads) while the device works on the next chunk; the records may be modified in place
 // (records of the chunk, their number, their offset in the result, number of the chunk)
 typedef std::function<void(dh_la *, int64_t, int64_t, int64_t)> ChunkHook;
+// dh_seed_candidates: the caller's arrays (item 0 = the first item of the call); with it a chunk ends behind its seeds
+struct SeedDump {
+    dh_seed_cand *cand;
+    int32_t *ncand, *nhits;
+};
 static int align_range(dh_ctx *ctx, dh_db *A, dh_db *B, int32_t first, int32_t count, const dh_align_opts *opts,
                        int32_t want_best, int32_t want_sorted, dh_la_set **out, const ChunkHook *hook = nullptr,
-                       dh_la_set **out_tr = nullptr);
+                       dh_la_set **out_tr = nullptr, const SeedDump *dump = nullptr);
 
 // `damapper <ref> <reads>.<block>` (snakemake/Snakefile:1143-1170): the reads [first, first + count)
 // of B against all of A; read ids in the records are those of the whole DB, as in a block's .las
@@ -120,6 +125,17 @@ int dh_align_db_ex(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_align_opts *opts, i
 {
     if (!B) return fail(DH_EINVAL, "dh_align_db: NULL argument");
     return align_range(ctx, A, B, 0, B->n, opts, want_best, want_sorted, out);
+}
+
+static_assert(sizeof(dh_seed_cand) == sizeof(DhCand), "dh_seed_cand is DhCand");
+// the seed stage of dh_align_db(ctx, A, B, opts) alone: align_range up to seed_chunk, every chunk's candidates copied out
+extern "C" int dh_seed_candidates(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_align_opts *opts, dh_seed_cand *cand,
+                                  int32_t *ncand, int32_t *nhits)
+{
+    if (!B || !cand || !ncand || !nhits) return fail(DH_EINVAL, "dh_seed_candidates: NULL argument");
+    const SeedDump dump{cand, ncand, nhits};
+    dh_la_set *none = nullptr;
+    return align_range(ctx, A, B, 0, B->n, opts, 0, 1, &none, nullptr, nullptr, &dump);
 }
 
 // derived copies (reverse complement, 2-bit packed forward / reverse) of the reads [r0, r1) of B in
@@ -1605,8 +1621,20 @@ static int finish_align(AlignRun &r, double wall0)
     return DH_OK;
 }
 
+// dh_seed_candidates: the seeds of the chunk as they stand in the scratch arena, into the caller's rows of its items
+static int dump_seeds(AlignRun &r, const AlignChunk &c, const SeedDump &d)
+{
+    const size_t at = (size_t)(c.item0 - r.item_first), ni = (size_t)c.ni;
+    HIPCHK(hipMemcpyAsync(d.cand + at * r.o.max_cand, r.d_cand, sizeof(DhCand) * ni * r.o.max_cand, hipMemcpyDeviceToHost, r.st));
+    HIPCHK(hipMemcpyAsync(d.ncand + at, r.d_ncand, sizeof(int32_t) * ni, hipMemcpyDeviceToHost, r.st));
+    HIPCHK(hipMemcpyAsync(d.nhits + at, r.d_nhits, sizeof(int32_t) * ni, hipMemcpyDeviceToHost, r.st));
+    HIPCHK(hipStreamSynchronize(r.st));
+    return DH_OK;
+}
+
 static int align_range(dh_ctx *ctx, dh_db *A, dh_db *B, int32_t first, int32_t count, const dh_align_opts *opts,
-                       int32_t want_best, int32_t want_sorted, dh_la_set **out, const ChunkHook *hook, dh_la_set **out_tr)
+                       int32_t want_best, int32_t want_sorted, dh_la_set **out, const ChunkHook *hook, dh_la_set **out_tr,
+                       const SeedDump *dump)
 {
     const double wall0 = now_ms() * 1e3;
     double w_a = now_ms();
@@ -1664,11 +1692,25 @@ static int align_range(dh_ctx *ctx, dh_db *A, dh_db *B, int32_t first, int32_t c
         if (int rc = seed_chunk(r, c, &redo)) return rc;
         if (redo) continue;  // the same chunk again (seed_chunk says why)
         r.lap(1);
+        if (dump) {  // dh_seed_candidates: the chunk ends here
+            if (int rc = dump_seeds(r, c, *dump)) return rc;
+            item0 += r.cn;
+            continue;
+        }
         if (int rc = extend_chunk(r, c)) return rc;
         if (int rc = gather_chunk(r, c)) return rc;
         item0 += r.cn;
     }
     r.w_loop = now_ms() - w_a;
+    if (dump) {  // the statistics of the seed stage alone (hits, cands, overflow_items, big_items, b_bases); no cumulative ones
+        for (int64_t it = 0; it < r.nitems_total; it++) {
+            r.stats.hits += dump->nhits[it];
+            r.stats.cands += std::max(dump->ncand[it], 0);
+            r.stats.overflow_items += dump->ncand[it] == -2;
+        }
+        ctx->stats = r.stats;
+        return DH_OK;
+    }
     if (int rc = finish_align(r, wall0)) return rc;
     *out = r.res.release();
     if (out_tr) *out_tr = r.res2.release();

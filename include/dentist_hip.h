@@ -196,6 +196,17 @@ int64_t dh_join_hit_capacity(const int64_t *bases, const int32_t *reads, int32_t
  */
 int dh_align_db(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_align_opts *opts, int32_t select_best,
                 dh_la_set **out);
+typedef struct { int32_t score, aseq, apos, bpos; } dh_seed_cand;   /* == DhCand */
+/* The seed stage of dh_align_db alone: for every item (2 * read + strand) of B the candidates as the extension would
+ * receive them, in stored order. cand: 2 * n(B) * opts->max_cand entries, row i = item i; ncand, nhits: 2 * n(B).
+ * Items of a strand that opts->strands leaves out: 0 / 0.  ncand -2: the seed filter gave up on the item (more than 256
+ * candidate band pairs; dh_align_db reports such reads as overflow).  The index, the joins, the tier selection, what the
+ * context learns and the counters (dh_get_seed_tier_counts, dh_get_mjoin_counts, dh_get_join_counts,
+ * dh_get_tjoin_counts) are those of the dh_align_db call with the same arguments; no alignment is computed.
+ * dh_get_align_stats then gives hits, cands, overflow_items, big_items and b_bases of the seed stage, the rest 0; the
+ * cumulative statistics do not count the call.  (Tests: which tier or join disagrees on which item.) */
+int dh_seed_candidates(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_align_opts *opts,
+                       dh_seed_cand *cand, int32_t *ncand, int32_t *nhits);
 /* select_best: damapper's chains.  The LAs of a read on one contig and strand that follow each other (gaps <= 10 kb,
  * gap difference <= 6 kb: a long indel splits a mapping into collinear LAs) form a chain: START (0x4) on its first
  * LA, NEXT (0x8) on the others, BEST (0x10) on the LAs of the chain that no higher-scoring chain of the strand covers

@@ -328,6 +328,47 @@ int oz_seed_candidates(const oz_index *ix, const oz_db *A, const uint8_t *b, int
     return seed_candidates(ix, b, blen, bgroup, bself, NULL, 0, o, out, nhits_out, o->skip_self == 2 && o->algo == 1 ? A->pflags : NULL);
 }
 
+/* mask of read r of B in the orientation of the strand (mirrored for the complement); *tmp: to be freed by the caller */
+static const int32_t *strand_mask(const oz_db *B, int32_t r, int32_t blen, int strand, int64_t *nbm, int32_t **tmp)
+{
+    *nbm = 0;
+    *tmp = NULL;
+    if (!B->mask_ptr) return NULL;
+    *nbm = B->mask_ptr[r + 1] - B->mask_ptr[r];
+    const int32_t *bm = B->mask_iv + 2 * B->mask_ptr[r];
+    if (strand && *nbm > 0) {
+        int32_t *t = (int32_t *)malloc((size_t)*nbm * 2 * sizeof(int32_t));
+        for (int64_t x = 0; x < *nbm; x++) {
+            t[2 * x] = blen - bm[2 * (*nbm - 1 - x) + 1];
+            t[2 * x + 1] = blen - bm[2 * (*nbm - 1 - x)];
+        }
+        *tmp = t;
+        bm = t;
+    }
+    return bm;
+}
+
+/* the seed stage of item (r, strand) of B exactly as align_read runs it (B's mask included); out: o->max_cand entries */
+int oz_seed_candidates_item(const oz_index *ix, const oz_db *A, const oz_db *B, int32_t r, int32_t strand,
+                            const oz_opts *o, oz_cand *out, int32_t *nhits_out)
+{
+    const uint8_t *bf = B->bases + B->off[r];
+    const int32_t blen = (int32_t)(B->off[r + 1] - B->off[r]);
+    uint8_t *rc = NULL;
+    if (strand) {
+        rc = (uint8_t *)malloc((size_t)blen + 1);
+        oz_revcomp(bf, blen, rc);
+    }
+    int64_t nbm = 0;
+    int32_t *tmpm = NULL;
+    const int32_t *bm = strand_mask(B, r, blen, strand, &nbm, &tmpm);
+    const int nc = seed_candidates(ix, strand ? rc : bf, blen, B->group ? B->group[r] : 0, r, bm, nbm, o, out, nhits_out,
+                                   o->skip_self == 2 && o->algo == 1 ? A->pflags : NULL);
+    free(tmpm);
+    free(rc);
+    return nc;
+}
+
 static int seed_candidates(const oz_index *ix, const uint8_t *b, int32_t blen, int32_t bgroup,
                            int32_t bself, const int32_t *bmask, int64_t nbmask, const oz_opts *o,
                            oz_cand *out, int32_t *nhits_out, const uint8_t *pflags)
@@ -991,22 +1032,9 @@ static void align_read(const oz_index *ix, const oz_db *A, const oz_db *B, int32
             b = rc;
         }
         int32_t nh = 0;
-        /* mask of this B read in the orientation of the strand (mirrored for the complement) */
-        const int32_t *bm = NULL;
         int64_t nbm = 0;
         int32_t *tmpm = NULL;
-        if (B->mask_ptr) {
-            nbm = B->mask_ptr[r + 1] - B->mask_ptr[r];
-            bm = B->mask_iv + 2 * B->mask_ptr[r];
-            if (strand && nbm > 0) {
-                tmpm = (int32_t *)malloc((size_t)nbm * 2 * sizeof(int32_t));
-                for (int64_t x = 0; x < nbm; x++) {
-                    tmpm[2 * x] = blen - bm[2 * (nbm - 1 - x) + 1];
-                    tmpm[2 * x + 1] = blen - bm[2 * (nbm - 1 - x)];
-                }
-                bm = tmpm;
-            }
-        }
+        const int32_t *bm = strand_mask(B, r, blen, strand, &nbm, &tmpm);
         const uint8_t *pf = o->skip_self == 2 && o->algo == 1 ? A->pflags : NULL;
         int nc = seed_candidates(ix, b, blen, bgroup, r, bm, nbm, o, cands, &nh, pf);
         free(tmpm);

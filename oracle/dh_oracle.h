@@ -128,6 +128,10 @@ int64_t oz_index_size(const oz_index *ix);
 int oz_seed_candidates(const oz_index *ix, const oz_db *A, const uint8_t *b, int32_t blen,
                        int32_t bgroup, int32_t bself, int32_t sepv, const oz_opts *o,
                        oz_cand *out, int32_t *nhits_out);
+/* the seed stage of item (read r, strand) of B as oz_align_db runs it, the mask of B included: the candidates in the order
+ * the extension takes them (out: o->max_cand entries), *nhits_out the k-mer hits of the item */
+int oz_seed_candidates_item(const oz_index *ix, const oz_db *A, const oz_db *B, int32_t r, int32_t strand,
+                            const oz_opts *o, oz_cand *out, int32_t *nhits_out);
 
 /* one local alignment through seed (as, bs); returns 1 and fills la/trace (trace capacity
  * >= 2*(alen/tspace+3)) when an alignment was produced (not yet filtered for length/error). */

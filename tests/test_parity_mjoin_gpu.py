@@ -3,7 +3,9 @@ dazzler.d:6158-6170) against the CPU oracle and against the directory lookups it
 hits per read, hence the same candidates, alignments and trace values.
 
 The join takes chunks of at least 64 Mbp by default; DH_MJOIN_MIN=0 sends the small inputs of these tests through it
-and dh_get_mjoin_counts tells that it ran."""
+and dh_get_mjoin_counts tells that it ran.
+
+The candidates themselves, item by item: tests/test_parity_seedstage_gpu.py."""
 import os
 
 import numpy as np

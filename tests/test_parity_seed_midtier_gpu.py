@@ -4,7 +4,9 @@ tier of a chunk of the mapping join or the table join whose reads have 342 to 1 
 the directory lookups (DH_NO_MJOIN=1): bit exact, whichever tier sorted a read's hits.  dh_get_seed_tier_counts tells
 whether the tier ran and how many reads were redone behind it.
 
-DH_MJOIN_MIN=0 sends the small inputs of these tests through the mapping join."""
+DH_MJOIN_MIN=0 sends the small inputs of these tests through the mapping join.
+
+The candidates themselves, item by item: tests/test_parity_seedstage_gpu.py."""
 import ctypes
 import os
 

@@ -1,7 +1,9 @@
 """The per-group k-mer table join that seeds a grouped template DB against a grouped read DB (csrc/dh_tjoin.h; the
 consensus re-alignment of `dentist process`) against the directory lookups it replaces (DH_NO_TJOIN=1) and against the
 CPU oracle -- bit exact: the same hits per read, hence the same candidates, records and trace values.
-dh_get_tjoin_counts tells which path ran."""
+dh_get_tjoin_counts tells which path ran.
+
+The candidates themselves, item by item: tests/test_parity_seedstage_gpu.py."""
 import os
 import re
 
