@@ -124,6 +124,10 @@ SYMBOLS = [
     "dh_region_result_span_ids", "dh_region_result_mask_ptr", "dh_region_result_mask_iv", "dh_region_result_mask_count",
     "dh_region_result_pairs", "dh_region_result_big_regions", "dh_region_result_groups",
     "dh_la_collect_filter", "dh_la_set_collect_filter",
+    "dh_la_repeat_mask", "dh_la_set_repeat_mask", "dh_repeat_result_destroy", "dh_repeat_result_mask_ptr", "dh_repeat_result_mask_iv",
+    "dh_repeat_result_mask_count", "dh_repeat_result_all_ptr", "dh_repeat_result_all_iv", "dh_repeat_result_all_count",
+    "dh_repeat_result_improper_ptr", "dh_repeat_result_improper_iv", "dh_repeat_result_improper_count", "dh_repeat_result_units",
+    "dh_repeat_result_improper_units", "dh_repeat_result_tier_contigs", "dh_repeat_result_groups",
 ]
 
 _LIB = None
@@ -303,6 +307,21 @@ def lib():
     for name in ("reports", "weak", "span_off", "span_ids", "mask_ptr", "mask_iv"):
         getattr(L, "dh_region_result_" + name).argtypes = [vp]
         getattr(L, "dh_region_result_" + name).restype = vp
+    L.dh_la_repeat_mask.argtypes = [vp, vp, i64, vp, i32, vp, i32, ctypes.POINTER(RepeatOpts), ctypes.POINTER(vp)]
+    L.dh_la_set_repeat_mask.argtypes = [vp, vp, vp, i32, vp, i32, ctypes.POINTER(RepeatOpts), ctypes.POINTER(vp)]
+    L.dh_repeat_result_destroy.argtypes = [vp]
+    L.dh_repeat_result_destroy.restype = None
+    for which in ("mask", "all", "improper"):
+        for name in ("ptr", "iv"):
+            getattr(L, "dh_repeat_result_%s_%s" % (which, name)).argtypes = [vp]
+            getattr(L, "dh_repeat_result_%s_%s" % (which, name)).restype = vp
+        getattr(L, "dh_repeat_result_%s_count" % which).argtypes = [vp]
+        getattr(L, "dh_repeat_result_%s_count" % which).restype = i64
+    for name in ("units", "improper_units", "groups"):
+        getattr(L, "dh_repeat_result_" + name).argtypes = [vp]
+        getattr(L, "dh_repeat_result_" + name).restype = i64
+    L.dh_repeat_result_tier_contigs.argtypes = [vp, i32]
+    L.dh_repeat_result_tier_contigs.restype = i64
     _LIB = L
     return L
 
@@ -713,6 +732,28 @@ class Context:
         _check(L.dh_la_collect_filter(self._h, arr.ctypes.data if len(arr) else None, len(arr), *tail))
         return arr, dropped, used
 
+    def repeat_mask(self, las, contig_off, read_off=None, lower=0, upper=4, improper=None, allowance=100):
+        """dh_la_repeat_mask: `dentist mask-repetitive-regions` (maskRepetitiveRegions.d:129-430) on the device, from records
+        sorted by aread and the lengths to intervals.  (lower, upper): the bounds of the assessor over all chains; improper:
+        None, or the (lower, upper) of the assessor over the improper chains (needs read_off).  Returns a RepeatMask.  `las`
+        may be a raw handle of align_db_block(..., raw=True) (dh_la_set_repeat_mask): the handle stays the caller's."""
+        co = np.ascontiguousarray(contig_off, dtype=np.int64)
+        ro = None if read_off is None else np.ascontiguousarray(read_off, dtype=np.int64)
+        if len(co) < 1 or (ro is not None and len(ro) < 1):
+            raise ValueError("contig_off and read_off need n + 1 entries")
+        o = RepeatOpts(int(lower), int(upper), 0, 0, int(allowance), 0)
+        if improper is not None:
+            o.improper_lower, o.improper_upper, o.with_improper = int(improper[0]), int(improper[1]), 1
+        h = ctypes.c_void_p()
+        tail = (co.ctypes.data, len(co) - 1, ro.ctypes.data if ro is not None else None, len(ro) - 1 if ro is not None else 0,
+                ctypes.byref(o), ctypes.byref(h))
+        if isinstance(las, ctypes.c_void_p):
+            _check(lib().dh_la_set_repeat_mask(self._h, las, *tail))
+        else:
+            arr = np.ascontiguousarray(las, dtype=LA_DTYPE)
+            _check(lib().dh_la_repeat_mask(self._h, arr.ctypes.data if len(arr) else None, len(arr), *tail))
+        return RepeatMask(h, len(co) - 1)
+
     def transpose(self, A, B, las, trace=None, tspace=None, select_best=False):
         """dh_la_transpose: the same alignments with the roles of the sequences exchanged (aread = B read, trace points on
         the B read's grid), from their edit paths.  Returns (las', trace', src_index), LAsort order; src_index[i] is the
@@ -823,6 +864,36 @@ class Chains:
                 self._h = None
         except Exception:
             pass
+
+
+class RepeatOpts(ctypes.Structure):
+    """dh_repeat_opts"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("lower", "upper", "improper_lower", "improper_upper", "allowance", "with_improper")]
+
+
+class RepeatMask:
+    """Result of Context.repeat_mask (copies): mask, all, improper as (ptr int64[ncontigs + 1], iv int32[m, 2]); units and
+    improper_units: the chains counted; tier_contigs[t]: contigs without events, of the wavefront, the LDS and the global
+    tier; groups: launch groups."""
+
+    def __init__(self, h, ncontigs):
+        L = lib()
+
+        def copy(ptr, shape, dtype):
+            a = np.zeros(shape, dtype=dtype)
+            if a.nbytes:
+                ctypes.memmove(a.ctypes.data, ptr, a.nbytes)
+            return a
+        try:
+            for which in ("mask", "all", "improper"):
+                m = int(getattr(L, "dh_repeat_result_%s_count" % which)(h))
+                setattr(self, which, (copy(getattr(L, "dh_repeat_result_%s_ptr" % which)(h), ncontigs + 1, np.int64),
+                                      copy(getattr(L, "dh_repeat_result_%s_iv" % which)(h), (m, 2), np.int32)))
+            self.units, self.improper_units = int(L.dh_repeat_result_units(h)), int(L.dh_repeat_result_improper_units(h))
+            self.tier_contigs = [int(L.dh_repeat_result_tier_contigs(h, t)) for t in range(4)]
+            self.groups = int(L.dh_repeat_result_groups(h))
+        finally:
+            L.dh_repeat_result_destroy(h)
 
 
 class PropagatedMask:

@@ -156,6 +156,15 @@ enum DhSlot : int {
     SLOT_CP_RECS, SLOT_CP_TRACE, SLOT_CP_CHAIN_OFF, SLOT_CP_NSEG, SLOT_CP_NTILE, SLOT_CP_NFILL, SLOT_CP_STATUS, SLOT_CP_SEGS,
     SLOT_CP_TILES, SLOT_CP_FILLS, SLOT_CP_TILE_OP, SLOT_CP_FILL_SRC, SLOT_CP_FILL_NOPS, SLOT_CP_FILL_OPS, SLOT_CP_LEN, SLOT_CP_OUT,
     SLOT_CP_SCORE, SLOT_CP_SUMS, SLOT_CP_TOTAL,
+    // repeat mask (dh_la_repeat_mask, dh_rmask.cpp).  SLOT_RM_ALEN / BLEN live for one call; the others are rewritten by every
+    // launch group: its compact records and the first record of each of its contigs (ROFF); SLOT_RM_FLAG / UID per record
+    // (starts a chain, the scanned flags with the number of units behind the last), SLOT_RM_SUMS the block sums of the scans;
+    // SLOT_RM_EV two keys per unit, SLOT_RM_SEG the key segment of every contig; SLOT_RM_CTR the counters and the number of
+    // units; the tier lists, the slab offsets of the global tier and its slab; per mask the run counts (then their scan) and
+    // the intervals
+    SLOT_RM_RECS, SLOT_RM_ALEN, SLOT_RM_BLEN, SLOT_RM_ROFF, SLOT_RM_FLAG, SLOT_RM_UID, SLOT_RM_SUMS, SLOT_RM_EV, SLOT_RM_SEG, SLOT_RM_CTR,
+    SLOT_RM_LWAVE, SLOT_RM_LLDS, SLOT_RM_LGLOB, SLOT_RM_SLAB_AT, SLOT_RM_SLAB, SLOT_RM_CNT_ALL, SLOT_RM_CNT_IMP, SLOT_RM_CNT_MASK,
+    SLOT_RM_IV_ALL, SLOT_RM_IV_IMP, SLOT_RM_IV_MASK,
     DH_SLOT_COUNT
 };
 // The words of SLOT_STATUS (DH_STW_COUNT x int32), one buffer with three users.  All of them run on the context's stream:

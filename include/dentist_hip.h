@@ -1079,6 +1079,66 @@ int dh_la_set_collect_filter(dh_ctx *ctx, dh_la_set *set, const int64_t *contig_
                              int32_t nreads, const int64_t *rep_ptr, const int32_t *rep_iv, const dh_process_opts *opts,
                              int64_t *dropped6, uint8_t *read_used);
 
+/* ---- `dentist mask-repetitive-regions` on the device (commands/maskRepetitiveRegions.d:129-430), from records and lengths to
+ *      intervals, without a dh_db; tools/mask-repetitive-regions is the drop-in of the command.  Kernels: csrc/dh_rmask.hip.
+ *   Units.  A unit is an alignment chain, as dh_la_collect_filter defines it: a record continues the chain of the record before
+ *      it iff it has NEXT without START and the same aread, bread and strand.  Its interval on contig aread is [abpos of its
+ *      first record, aepos of its last record): the gaps between the members are covered.  It is proper within `allowance` iff
+ *      (abpos <= allowance || bbpos <= allowance) && (aepos + allowance >= alen || bepos + allowance >= blen) with the first
+ *      record's begins and the last record's ends (base.d:537-557; the Improper rule of the collect filters).  DH_FLAG_DISABLED
+ *      is not looked at.
+ *   One assessor (BadAlignmentCoverageAssessor.opCall :344-391) with bounds (lower, upper): cov(c, p) = the counted units of
+ *      contig c whose interval contains base p; base p of [0, len(c)) is bad iff cov < lower || cov > upper; the result is the
+ *      maximal runs of bad bases per contig -- ascending, disjoint, never touching.  A contig without counted units is one run
+ *      [0, len) iff 0 < lower.  An assessor that counts no unit at all gives nothing (:350-351).
+ *   The call.  all = the assessor over every unit with (lower, upper); improper = the assessor over the units that are not
+ *      proper with (improper_lower, improper_upper), only if with_improper (the reads case :160-180); mask = all | improper, the
+ *      ReferenceRegion union: intersecting or touching intervals are merged (util/region.d:776-816).  Without with_improper,
+ *      improper is empty and mask = all.
+ *   Input.  Records sorted at least by aread with the members of a chain consecutive (LAsort order).  contig_off[ncontigs + 1]
+ *      and read_off[nreads + 1] give the lengths; read_off may be NULL iff with_improper == 0.
+ *   Refusals, all made on the host before anything is launched, naming the lowest offending index: DH_EINVAL "bad argument" for
+ *      a NULL pointer, a negative count or opts missing; DH_EINVAL for lower > upper, improper_lower > improper_upper, a negative
+ *      bound or allowance; DH_EINVAL naming the lowest contig longer than 2^31 - 1; DH_EINVAL naming the lowest record with
+ *      aread (with_improper: or bread) out of range, aread below the record before it, abpos < 0, abpos > aepos, aepos behind
+ *      the contig's end, or that starts a chain whose last aepos lies before its first abpos; DH_EINVAL naming the lowest
+ *      contig with more than 2^29 records; DH_EOVERFLOW for 2^30 records or more.  n == 0 is no error: three empty masks, no launch.
+ *   How.  Per launch group (whole contigs, as many as DH_RMASK_CHUNK_MB hold; one contig always fits): one lane per record finds
+ *      the chain starts, a scan numbers the chains; the lane of a chain start writes two keys position << 2 | is_end << 1 |
+ *      improper -- records are grouped by aread, so a contig's keys are consecutive without a partition pass; a contig of up to
+ *      64 events is sorted by one wavefront in registers, of up to DH_RMASK_LDS_EVENTS by one workgroup in LDS, of more by the
+ *      same network on a slab of global memory, one launch per step over all workgroups; one wavefront per contig walks the sorted keys with two running sums and counts,
+ *      then (after a scan) places the runs without atomics; one lane per contig merges the two lists.  No contig falls back to
+ *      the host, nothing is sized by bases.  The result does not depend on the knobs and is the same from run to run.
+ *      Development knobs (tests): DH_RMASK_LDS_EVENTS, 1024 .. 8192 (default 8192); DH_RMASK_CHUNK_MB, a decimal number of MiB
+ *      (default 1024).
+ *   Result.  Per mask (mask, all, improper): ptr[ncontigs + 1], (begin, end) pairs, their number.  Counters (tests): units,
+ *      improper units (0 without with_improper), contigs per tier (0 no event, 1 wavefront, 2 LDS, 3 global), launch groups.
+ *   Unpinned.  Nothing: every interval is pinned to the restatement tests/repeat_ref.py over oracle/maskcov.py
+ *      (tests/test_parity_repeat_gpu.py). */
+typedef struct dh_repeat_opts {
+    int32_t lower, upper, improper_lower, improper_upper, allowance, with_improper;
+} dh_repeat_opts;
+typedef struct dh_repeat_result dh_repeat_result;
+int dh_la_repeat_mask(dh_ctx *ctx, const dh_la *las, int64_t n, const int64_t *contig_off, int32_t ncontigs, const int64_t *read_off,
+                      int32_t nreads, const dh_repeat_opts *opts, dh_repeat_result **out);
+int dh_la_set_repeat_mask(dh_ctx *ctx, const dh_la_set *set, const int64_t *contig_off, int32_t ncontigs, const int64_t *read_off,
+                          int32_t nreads, const dh_repeat_opts *opts, dh_repeat_result **out);
+void dh_repeat_result_destroy(dh_repeat_result *r);
+const int64_t *dh_repeat_result_mask_ptr(const dh_repeat_result *r);      /* ncontigs + 1 */
+const int32_t *dh_repeat_result_mask_iv(const dh_repeat_result *r);       /* (begin, end) pairs */
+int64_t dh_repeat_result_mask_count(const dh_repeat_result *r);
+const int64_t *dh_repeat_result_all_ptr(const dh_repeat_result *r);
+const int32_t *dh_repeat_result_all_iv(const dh_repeat_result *r);
+int64_t dh_repeat_result_all_count(const dh_repeat_result *r);
+const int64_t *dh_repeat_result_improper_ptr(const dh_repeat_result *r);
+const int32_t *dh_repeat_result_improper_iv(const dh_repeat_result *r);
+int64_t dh_repeat_result_improper_count(const dh_repeat_result *r);
+int64_t dh_repeat_result_units(const dh_repeat_result *r);                /* chains (tests) */
+int64_t dh_repeat_result_improper_units(const dh_repeat_result *r);       /* chains that are not proper (tests) */
+int64_t dh_repeat_result_tier_contigs(const dh_repeat_result *r, int32_t tier); /* contigs of tier 0..3 (tests) */
+int64_t dh_repeat_result_groups(const dh_repeat_result *r);               /* launch groups (tests) */
+
 /* ---- gap-closed assembly writer (host only): the linear-scaffold subset of `dentist output`
  *      (source/dentist/commands/output.d:743-925): header "<id>\tscaffold-<first contig id>", contig
  *      slices lower case, insertions upper case (highlight != 0), unclosed gaps as 'n' runs, lines

@@ -59,6 +59,12 @@
 //                                    the alignments filtered on the device (dh_la_collect_filter), the scaffold graph with its
 //                                    bubbles resolved, every pile-up written to <pile-ups.db> (`dentist collect`,
 //                                    commands/collectPileUps/package.d:88-206; snakemake/Snakefile:1257-1290)
+//   mask-repetitive-regions [--read-coverage=<f> | --max-coverage-reads=<n>] [--max-improper-coverage-reads=<n>]
+//           [--max-coverage-self=<n>] [--proper-alignment-allowance=<n>] [--debug-repeat-masks] <ref-db> [<reads-db>] <db-alignment>
+//           <repeat-mask>           the mask of the contig bases whose coverage by alignment chains (with <reads-db>: also by the
+//                                    improper ones) leaves its bounds, written as a mask track of <ref-db>
+//                                    (dh_la_repeat_mask: `dentist mask-repetitive-regions`, commands/maskRepetitiveRegions.d:
+//                                    129-430, commandline.d:1840-1972)
 // DENTIST only sees exit codes, files and stdout of these tools; flags it never emits are rejected.
 #include <algorithm>
 #include <cmath>
@@ -1763,6 +1769,114 @@ static int tool_collect(const std::vector<std::string> &args)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- mask-repetitive-regions
+// Unknown options and the reference's option validation (commandline.d:1840-1972): the message and exit 1.  Everything else that
+// fails: the library's message and exit 2.
+static int tool_mask_repetitive_regions(const std::vector<std::string> &args)
+{
+    const std::string usage = "usage: mask-repetitive-regions [--read-coverage=<f> | --max-coverage-reads=<n>] [--max-improper-coverage-reads=<n>] "
+                              "[--max-coverage-self=<n>] [--proper-alignment-allowance=<n>] [--debug-repeat-masks] [--config=<file>] [-v] "
+                              "[--quiet] [-T<n>] <ref-db> [<reads-db>] <db-alignment> <repeat-mask>";
+    auto fail = [](const std::string &what) {
+        fprintf(stderr, "mask-repetitive-regions: %s\n", what.c_str());
+        return 2;
+    };
+    std::vector<std::string> pos;
+    bool ignored = false, debug_masks = false, has_cov = false, has_max = false, has_max_improper = false, has_allowance = false;
+    double read_coverage = 0.0;
+    long long max_reads = 0, max_improper = 0, max_self = 4, allowance = 0;
+    auto number = [&](const std::string &a, size_t at, long long *out) {
+        char *end = nullptr;
+        *out = strtoll(a.c_str() + at, &end, 10);
+        if (end == a.c_str() + at || *end || *out < 0 || *out > INT32_MAX) die("unknown or malformed option " + a + "\n" + usage);
+    };
+    auto starts = [](const std::string &a, const char *p) { return a.size() > strlen(p) && a.compare(0, strlen(p), p) == 0; };
+    for (const std::string &a : args) {
+        if (starts(a, "--read-coverage=")) {
+            char *end = nullptr;
+            read_coverage = strtod(a.c_str() + 16, &end);
+            if (end == a.c_str() + 16 || *end || !(read_coverage > 0.0)) die("unknown or malformed option " + a + "\n" + usage);
+            has_cov = true;
+        } else if (starts(a, "--max-coverage-reads="))
+            number(a, 21, &max_reads), has_max = true;
+        else if (starts(a, "--max-improper-coverage-reads="))
+            number(a, 30, &max_improper), has_max_improper = true;
+        else if (starts(a, "--max-coverage-self="))
+            number(a, 20, &max_self);
+        else if (starts(a, "--proper-alignment-allowance="))
+            number(a, 29, &allowance), has_allowance = true;
+        else if (a == "--debug-repeat-masks")
+            debug_masks = true;
+        else if (a == "-v" || a == "--quiet" || starts(a, "--config=") || starts(a, "-T") || starts(a, "--threads="))
+            ignored = true;
+        else if (a.size() > 1 && a[0] == '-')
+            die("unknown or malformed option " + a + "\n" + usage);
+        else
+            pos.push_back(a);
+    }
+    if (pos.size() != 3 && pos.size() != 4) die(usage);
+    const bool reads_case = pos.size() == 4;
+    if (reads_case) {  // commandline.d:1868-1875, 1948-1955
+        if (!has_max && !has_cov) die("must provide either --read-coverage or --max-coverage-reads");
+        if (has_max && has_cov) die("must not provide both --read-coverage and --max-coverage-reads");
+        if (!has_max_improper && !has_cov) die("must provide either --read-coverage or --max-improper-coverage-reads");
+        if (has_max_improper && has_cov) die("must not provide both --read-coverage and --max-improper-coverage-reads");
+    } else if (max_self < 1)
+        die("--max-coverage-self must be positive");
+    if (ignored) fprintf(stderr, "mask-repetitive-regions: --config, -v, --quiet, -T and --threads have no effect here\n");
+    const std::string &in = pos[pos.size() - 2], &out_name = pos[pos.size() - 1];
+    dh_dazz *da = nullptr, *db = nullptr;
+    if (dh_dazz_open(pos[0].c_str(), &da)) return fail(dh_last_error());
+    if (reads_case && dh_dazz_open(pos[1].c_str(), &db)) return fail(dh_last_error());
+    const dh_dazz *other = db ? db : da;  // (a self alignment has the contigs on both sides)
+    const int32_t ncontigs = dh_dazz_nreads(da), nreads = dh_dazz_nreads(other);
+    dh_la_set *set = nullptr;
+    if (dh_las_read(in.c_str(), &set)) return fail(dh_last_error());
+    const int64_t n = dh_la_set_count(set);
+    if (n == 0) fprintf(stderr, "mask-repetitive-regions: warning: empty %s-alignment\n", reads_case ? "reads" : "self");
+    std::vector<dh_la> las(dh_la_set_records(set), dh_la_set_records(set) + n);
+    for (dh_la &l : las) {  // ids of the opened views
+        l.aread -= dh_dazz_first_id(da);
+        l.bread -= dh_dazz_first_id(other);
+    }
+    dh_repeat_opts o;
+    o.lower = 0, o.improper_lower = 0, o.with_improper = reads_case ? 1 : 0;
+    o.upper = reads_case ? (has_cov ? dh_max_coverage_reads(read_coverage) : (int32_t)max_reads) : (int32_t)max_self;
+    o.improper_upper = reads_case ? (has_cov ? dh_max_improper_coverage_reads(read_coverage) : (int32_t)max_improper) : 0;
+    o.allowance = has_allowance ? (int32_t)allowance : dh_la_set_tspace(set);
+    dh_ctx *ctx = nullptr;
+    dh_repeat_result *res = nullptr;
+    if (n > 0 && dh_ctx_create(0, nullptr, &ctx)) return fail(dh_last_error());
+    static const int32_t no_iv[2] = {0, 0};
+    if (n > 0) {
+        if (dh_la_repeat_mask(ctx, las.data(), n, dh_dazz_offsets(da), ncontigs, dh_dazz_offsets(other), nreads, &o, &res)) return fail(dh_last_error());
+        auto write = [&](const std::string &name, const int64_t *ptr, const int32_t *iv, int64_t count) {
+            return dh_dazz_write_mask(pos[0].c_str(), name.c_str(), ncontigs, ptr, count > 0 ? iv : no_iv);
+        };
+        if (write(out_name, dh_repeat_result_mask_ptr(res), dh_repeat_result_mask_iv(res), dh_repeat_result_mask_count(res)))
+            return fail(dh_last_error());
+        if (debug_masks && reads_case) {  // maskRepetitiveRegions.d:225-237
+            if (write(out_name + "-all", dh_repeat_result_all_ptr(res), dh_repeat_result_all_iv(res), dh_repeat_result_all_count(res)) ||
+                write(out_name + "-improper", dh_repeat_result_improper_ptr(res), dh_repeat_result_improper_iv(res),
+                      dh_repeat_result_improper_count(res)))
+                return fail(dh_last_error());
+        }
+        dh_repeat_result_destroy(res);
+    } else {  // an empty mask, without a device
+        const std::vector<int64_t> ptr((size_t)ncontigs + 1, 0);
+        if (dh_dazz_write_mask(pos[0].c_str(), out_name.c_str(), ncontigs, ptr.data(), no_iv)) return fail(dh_last_error());
+        if (debug_masks && reads_case)
+            if (dh_dazz_write_mask(pos[0].c_str(), (out_name + "-all").c_str(), ncontigs, ptr.data(), no_iv) ||
+                dh_dazz_write_mask(pos[0].c_str(), (out_name + "-improper").c_str(), ncontigs, ptr.data(), no_iv))
+                return fail(dh_last_error());
+    }
+    dh_la_set_destroy(set);
+    if (db) dh_dazz_close(db);
+    dh_dazz_close(da);
+    if (ctx) dh_ctx_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     g_tool = argv[0];
@@ -1799,7 +1913,9 @@ int main(int argc, char **argv)
     if (g_tool == "propagate-mask") return tool_propagate_mask(args);
     if (g_tool == "validate-regions") return tool_validate_regions(args);
     if (g_tool == "collect") return tool_collect(args);
+    if (g_tool == "mask-repetitive-regions") return tool_mask_repetitive_regions(args);
     die("unknown tool (expected fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv "
-        "computeintrinsicqv daccord merge-insertions)");
+        "computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index "
+        "chain-local-alignments propagate-mask validate-regions collect mask-repetitive-regions)");
     return 1;
 }
