@@ -6,7 +6,7 @@ CSRC := dentist_amd/csrc
 LIB := dentist_amd/libdentist_hip.so
 SIM := dentist_amd/sim/libdh_sim.so
 
-DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index chain-local-alignments propagate-mask validate-regions collect mask-repetitive-regions
+DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index chain-local-alignments propagate-mask validate-regions collect mask-repetitive-regions merge-masks filter-mask
 TOOLS := tools/daligner tools/damapper tools/datander tools/dazz_tools $(addprefix tools/,$(DAZZ_TOOLS))
 
 all: $(LIB) $(SIM) oracle $(TOOLS)
@@ -151,3 +151,13 @@ tests/native/librmask_host.so: tests/native/rmask_host.cpp dentist_amd/csrc/dh_r
 # interval of a contig's runs are where this code would overrun
 tests/native/rmask_host_san: tests/native/rmask_host_main.cpp tests/native/rmask_host.cpp dentist_amd/csrc/dh_rmask.h dentist_amd/csrc/dh_cfilt.h include/dentist_hip.h
 	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/rmask_host_main.cpp tests/native/rmask_host.cpp
+
+# the lane code and the host plan of the mask algebra (dentist_amd/csrc/dh_maskops.h) compiled for the CPU: test infrastructure
+tests/native/libmaskops_host.so: tests/native/maskops_host.cpp dentist_amd/csrc/dh_maskops.h include/dentist_hip.h
+	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -o $@ $<
+
+# the same harness and a stand-alone main under the host sanitizers (a program of its own: nothing is preloaded); run it once
+# after a change to dh_maskops.h -- the last key of a tile, the entry behind the last of the scanned words, the last run and
+# the last offset are where this code would overrun
+tests/native/maskops_host_san: tests/native/maskops_host_main.cpp tests/native/maskops_host.cpp dentist_amd/csrc/dh_maskops.h include/dentist_hip.h
+	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/maskops_host_main.cpp tests/native/maskops_host.cpp

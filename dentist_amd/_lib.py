@@ -128,6 +128,8 @@ SYMBOLS = [
     "dh_repeat_result_mask_count", "dh_repeat_result_all_ptr", "dh_repeat_result_all_iv", "dh_repeat_result_all_count",
     "dh_repeat_result_improper_ptr", "dh_repeat_result_improper_iv", "dh_repeat_result_improper_count", "dh_repeat_result_units",
     "dh_repeat_result_improper_units", "dh_repeat_result_tier_contigs", "dh_repeat_result_groups",
+    "dh_default_mask_opts", "dh_mask_combine", "dh_la_tandem_mask", "dh_mask_set_destroy", "dh_mask_set_ptr", "dh_mask_set_iv",
+    "dh_mask_set_count", "dh_mask_set_events", "dh_mask_set_sort_passes", "dh_mask_set_groups",
 ]
 
 _LIB = None
@@ -322,6 +324,18 @@ def lib():
         getattr(L, "dh_repeat_result_" + name).restype = i64
     L.dh_repeat_result_tier_contigs.argtypes = [vp, i32]
     L.dh_repeat_result_tier_contigs.restype = i64
+    L.dh_default_mask_opts.argtypes = [ctypes.POINTER(MaskOpts)]
+    L.dh_default_mask_opts.restype = None
+    L.dh_mask_combine.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, ctypes.POINTER(MaskOpts), ctypes.POINTER(vp)]
+    L.dh_la_tandem_mask.argtypes = [vp, vp, i64, vp, i32, i32, i32, ctypes.POINTER(vp)]
+    L.dh_mask_set_destroy.argtypes = [vp]
+    L.dh_mask_set_destroy.restype = None
+    for name in ("ptr", "iv"):
+        getattr(L, "dh_mask_set_" + name).argtypes = [vp]
+        getattr(L, "dh_mask_set_" + name).restype = vp
+    for name in ("count", "events", "sort_passes", "groups"):
+        getattr(L, "dh_mask_set_" + name).argtypes = [vp]
+        getattr(L, "dh_mask_set_" + name).restype = i64
     _LIB = L
     return L
 
@@ -754,6 +768,44 @@ class Context:
             _check(lib().dh_la_repeat_mask(self._h, arr.ctypes.data if len(arr) else None, len(arr), *tail))
         return RepeatMask(h, len(co) - 1)
 
+    def combine_masks(self, masks, contig_off, min_count=1, subtract=None, min_gap=0, min_interval=0):
+        """dh_mask_combine: `dentist merge-masks` / `filter-mask` and the ReferenceRegion operators on the device.  masks: a list
+        of (ptr int64[ncontigs + 1], iv (begin, end) pairs), intervals in any order; a base is kept iff at least min_count masks
+        have it (1: union, len(masks): intersection) and `subtract` (one such pair, or None) does not; then gaps up to min_gap
+        are closed, then runs shorter than min_interval dropped.  Returns a MaskSet."""
+        co = np.ascontiguousarray(contig_off, dtype=np.int64)
+        if len(co) < 1:
+            raise ValueError("contig_off needs n + 1 entries")
+
+        def pair(m):
+            ptr = np.ascontiguousarray(m[0], dtype=np.int64)
+            if len(ptr) != len(co):
+                raise ValueError("a mask's ptr needs ncontigs + 1 entries")
+            iv = np.ascontiguousarray(m[1], dtype=np.int32).reshape(-1)
+            return ptr, iv if len(iv) else np.zeros(2, dtype=np.int32)   # (never an empty array)
+        keep = [pair(m) for m in masks]
+        sub = pair(subtract) if subtract is not None else None
+        ptrs = (ctypes.c_void_p * max(len(keep), 1))(*[k[0].ctypes.data for k in keep])
+        ivs = (ctypes.c_void_p * max(len(keep), 1))(*[k[1].ctypes.data for k in keep])
+        o = MaskOpts(int(min_count), int(min_gap), int(min_interval), 0)
+        h = ctypes.c_void_p()
+        _check(lib().dh_mask_combine(self._h, ptrs, ivs, len(keep), sub[0].ctypes.data if sub else None, sub[1].ctypes.data if sub else None,
+                                     co.ctypes.data, len(co) - 1, ctypes.byref(o), ctypes.byref(h)))
+        return MaskSet(h, len(co) - 1)
+
+    def tandem_mask(self, las, read_off, first_read=0, min_len=500):
+        """dh_la_tandem_mask: TANmask's rule on the device -- the union of [min(abpos, bbpos), max(aepos, bepos)) over the
+        records with aread == bread on the same strand that are at least min_len long, per read aread - first_read.  Returns
+        a MaskSet indexed by read."""
+        ro = np.ascontiguousarray(read_off, dtype=np.int64)
+        if len(ro) < 1:
+            raise ValueError("read_off needs n + 1 entries")
+        arr = np.ascontiguousarray(las, dtype=LA_DTYPE)
+        h = ctypes.c_void_p()
+        _check(lib().dh_la_tandem_mask(self._h, arr.ctypes.data if len(arr) else None, len(arr), ro.ctypes.data, len(ro) - 1, int(first_read),
+                                       int(min_len), ctypes.byref(h)))
+        return MaskSet(h, len(ro) - 1)
+
     def transpose(self, A, B, las, trace=None, tspace=None, select_best=False):
         """dh_la_transpose: the same alignments with the roles of the sequences exchanged (aread = B read, trace points on
         the B read's grid), from their edit paths.  Returns (las', trace', src_index), LAsort order; src_index[i] is the
@@ -894,6 +946,29 @@ class RepeatMask:
             self.groups = int(L.dh_repeat_result_groups(h))
         finally:
             L.dh_repeat_result_destroy(h)
+
+
+class MaskOpts(ctypes.Structure):
+    """dh_mask_opts"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("min_count", "min_gap", "min_interval", "pad_")]
+
+
+class MaskSet:
+    """Result of Context.combine_masks / tandem_mask (copies): ptr int64[ncontigs + 1], iv int32[m, 2]; events: keys written
+    (twice the non-empty intervals given); sort_passes: radix passes run; groups: launch groups."""
+
+    def __init__(self, h, ncontigs):
+        L = lib()
+        try:
+            m = int(L.dh_mask_set_count(h))
+            self.ptr, self.iv = np.zeros(ncontigs + 1, dtype=np.int64), np.zeros((m, 2), dtype=np.int32)
+            ctypes.memmove(self.ptr.ctypes.data, L.dh_mask_set_ptr(h), self.ptr.nbytes)
+            if m:
+                ctypes.memmove(self.iv.ctypes.data, L.dh_mask_set_iv(h), self.iv.nbytes)
+            self.events, self.sort_passes, self.groups = (int(L.dh_mask_set_events(h)), int(L.dh_mask_set_sort_passes(h)),
+                                                          int(L.dh_mask_set_groups(h)))
+        finally:
+            L.dh_mask_set_destroy(h)
 
 
 class PropagatedMask:

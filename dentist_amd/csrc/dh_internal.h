@@ -165,6 +165,9 @@ enum DhSlot : int {
     SLOT_RM_RECS, SLOT_RM_ALEN, SLOT_RM_BLEN, SLOT_RM_ROFF, SLOT_RM_FLAG, SLOT_RM_UID, SLOT_RM_SUMS, SLOT_RM_EV, SLOT_RM_SEG, SLOT_RM_CTR,
     SLOT_RM_LWAVE, SLOT_RM_LLDS, SLOT_RM_LGLOB, SLOT_RM_SLAB_AT, SLOT_RM_SLAB, SLOT_RM_CNT_ALL, SLOT_RM_CNT_IMP, SLOT_RM_CNT_MASK,
     SLOT_RM_IV_ALL, SLOT_RM_IV_IMP, SLOT_RM_IV_MASK,
+    // mask algebra (dh_mask_combine, dh_la_tandem_mask, dh_maskops.cpp): every buffer of a launch group, carved from one request
+    // (the input, the keys twice, the scanned words, the boundaries, the runs in two stages, the output)
+    SLOT_MO_WORK,
     DH_SLOT_COUNT
 };
 // The words of SLOT_STATUS (DH_STW_COUNT x int32), one buffer with three users.  All of them run on the context's stream:

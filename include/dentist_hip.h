@@ -1139,6 +1139,66 @@ int64_t dh_repeat_result_improper_units(const dh_repeat_result *r);       /* cha
 int64_t dh_repeat_result_tier_contigs(const dh_repeat_result *r, int32_t tier); /* contigs of tier 0..3 (tests) */
 int64_t dh_repeat_result_groups(const dh_repeat_result *r);               /* launch groups (tests) */
 
+/* ---- mask algebra on the device: `dentist merge-masks` (commands/mergeMasks.d:47-53), `dentist filter-mask`
+ *      (commands/filterMask.d:124-159) and the ReferenceRegion operators | & - (util/region.d:776-1149) as one call;
+ *      tools/merge-masks and tools/filter-mask are the drop-ins of the commands.  Kernels: csrc/dh_maskops.hip.
+ *   Input.  nmasks >= 1 masks, each as ptr[ncontigs + 1] plus (begin, end) pairs: the layout of dh_dazz_read_mask and of every
+ *      mask result of the library.  Within a contig the intervals come in any order and may overlap, nest, touch, repeat or be
+ *      empty (begin == end), as the ReferenceRegion constructor takes them.  sub_ptr / sub_iv: the mask to subtract, both NULL
+ *      for none.  contig_off[ncontigs + 1] gives the lengths.
+ *   Semantics, per contig c and base p of [0, len(c)).  cov(p) = the number of input masks with at least one interval that
+ *      contains p: a mask counts once, however many of its intervals have p.  sub(p) = an interval of the subtract mask
+ *      contains p.  p is kept iff cov(p) >= min_count && !sub(p).  min_count 1 is |, min_count nmasks is &, the subtract mask -.
+ *      The result, in this order: (1) the maximal runs of kept bases, ascending, disjoint, never touching (normalize: intersecting
+ *      or touching intervals are merged; empty intervals have no effect); (2) gaps closed as filterMask.d:124-147 does: a run is
+ *      joined to the accumulated run before it iff it is on the same contig and acc.end + min_gap >= begin -- a gap of exactly
+ *      min_gap is closed, joining cascades; (3) what is shorter than min_interval is dropped (:150-159), a size equal to it stays.
+ *      Threshold and subtraction come first, so a closed gap may cover subtracted bases again.
+ *   Tandem rule.  dh_la_tandem_mask does what tools/TANmask does on the host: a record counts iff aread == bread and
+ *      DH_FLAG_COMP is not set; its interval is [min(abpos, bbpos), max(aepos, bepos)) on read aread - first_read and counts only
+ *      if it is at least min_len long (and not empty); the union is taken, touching intervals merged; the result is indexed by
+ *      read, read_off[nreads + 1] in the role of contig_off.  The records need no order.
+ *   Refusals, all made on the host before anything is launched, naming the lowest offending mask ("subtract mask" for that one),
+ *      contig or interval: DH_EINVAL "bad argument" for a NULL pointer, nmasks < 1 or a negative count; DH_EINVAL for
+ *      min_count < 1, min_count > nmasks, a negative min_gap or min_interval; a contig longer than 2^31 - 1 or a contig_off that
+ *      decreases; a ptr that does not start at 0 or decreases; begin < 0, begin > end, end behind the contig's end; tandem only: a
+ *      counted record whose aread lies outside [first_read, first_read + nreads) or whose interval runs past the read's end.
+ *      DH_EOVERFLOW for 2^30 intervals (records) or more, or when masks x contigs x the longest contig do not fit a 64-bit key.
+ *      No interval at all is no error: an empty set, no launch.
+ *   How.  Per launch group (whole contigs, as many as DH_MASKOPS_CHUNK_MB hold; one contig always fits; dh_la_tandem_mask is
+ *      one group): one lane per interval writes two 64-bit keys contig << (posbits + 2) | pos << 2 | is_subtract << 1 | is_end
+ *      (posbits from the group's longest contig); a device-wide stable LSD radix sort, 8-bit digits, only the digits in use
+ *      (histogram per tile, one scan, scatter by a rank from wave ballots -- no atomic decides an order); a device-wide sweep:
+ *      two scans give coverage and subtract depth behind every event, the last event of each distinct (contig, pos) is a
+ *      boundary, boundaries are compacted, a run begins where kept turns on and ends where it turns off; head flags, a scan and
+ *      compaction close the gaps, a size flag, a scan and compaction drop the short runs; one lane per contig finds its first
+ *      run by a binary search.  With min_count > 1 every mask is normalised on its own first: the same sort and sweep over
+ *      keys with mask * contigs + contig in front, min_count 1, whose runs are the events of the second sweep.  No step is
+ *      organised per contig: the cost does not depend on how the intervals are spread over the contigs.  The result does not
+ *      depend on the knobs and is the same from run to run.  Development knobs (tests): DH_MASKOPS_TILE_KEYS, 256 .. 2048 keys
+ *      per workgroup tile of the sort (default 2048); DH_MASKOPS_CHUNK_MB, a decimal number of MiB (default 1024).
+ *   Result.  ptr[ncontigs + 1], (begin, end) pairs, their number.  Counters (tests): events = twice the non-empty intervals
+ *      given (subtract mask included); sort_passes = the radix passes run, over all groups and both sorts; launch groups (those
+ *      that launched).
+ *   Unpinned.  Nothing: every interval is pinned to the restatement tests/maskops_ref.py, which is pinned to the reference's
+ *      own unit vectors (tests/golden/region_cases.json). */
+typedef struct dh_mask_opts {
+    int32_t min_count, min_gap, min_interval, pad_;
+} dh_mask_opts;
+void dh_default_mask_opts(dh_mask_opts *o); /* 1, 0, 0 */
+typedef struct dh_mask_set dh_mask_set;
+int dh_mask_combine(dh_ctx *ctx, const int64_t *const *ptr, const int32_t *const *iv, int32_t nmasks, const int64_t *sub_ptr,
+                    const int32_t *sub_iv, const int64_t *contig_off, int32_t ncontigs, const dh_mask_opts *opts, dh_mask_set **out);
+int dh_la_tandem_mask(dh_ctx *ctx, const dh_la *las, int64_t n, const int64_t *read_off, int32_t nreads, int32_t first_read,
+                      int32_t min_len, dh_mask_set **out);
+void dh_mask_set_destroy(dh_mask_set *s);
+const int64_t *dh_mask_set_ptr(const dh_mask_set *s);      /* ncontigs + 1 */
+const int32_t *dh_mask_set_iv(const dh_mask_set *s);       /* (begin, end) pairs */
+int64_t dh_mask_set_count(const dh_mask_set *s);
+int64_t dh_mask_set_events(const dh_mask_set *s);          /* keys written (tests) */
+int64_t dh_mask_set_sort_passes(const dh_mask_set *s);     /* radix passes (tests) */
+int64_t dh_mask_set_groups(const dh_mask_set *s);          /* launch groups (tests) */
+
 /* ---- gap-closed assembly writer (host only): the linear-scaffold subset of `dentist output`
  *      (source/dentist/commands/output.d:743-925): header "<id>\tscaffold-<first contig id>", contig
  *      slices lower case, insertions upper case (highlight != 0), unclosed gaps as 'n' runs, lines

@@ -1877,6 +1877,150 @@ static int tool_mask_repetitive_regions(const std::vector<std::string> &args)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- merge-masks, filter-mask
+// Mask track `name` of the whole DB `da` as ptr / iv (iv never an empty array).  `<block>.<mask>` with a block of the DB names
+// the track of that block (Snakefile:583-584): its reads are shifted by the block's first id into the whole DB's contig range.
+// Returns "" or what failed.
+static std::string read_mask_track(const dh_dazz *da, const std::string &db_path, const std::string &name, std::vector<int64_t> &ptr,
+                                   std::vector<int32_t> &iv)
+{
+    const int32_t ncontigs = dh_dazz_nreads(da);
+    ptr.assign((size_t)ncontigs + 1, 0);
+    const int64_t cnt = dh_dazz_read_mask(da, db_path.c_str(), name.c_str(), ptr.data(), nullptr, 0);
+    if (cnt < 0) return "mask " + name + ": " + dh_last_error();
+    iv.assign((size_t)(2 * cnt) + 2, 0);
+    if (dh_dazz_read_mask(da, db_path.c_str(), name.c_str(), ptr.data(), iv.data(), cnt) < 0) return "mask " + name + ": " + dh_last_error();
+    const size_t dot = name.find('.');
+    if (dot == std::string::npos || dot == 0 || name.find_first_not_of("0123456789") != dot) return "";
+    const DbPath d = parse_db_path(db_path);
+    const int32_t block = atoi(name.c_str());
+    if (block < 1 || block > stub_blocks(d)) return "";
+    dh_dazz *blk = nullptr;  // opened as TANmask opens the block of its .las
+    if (dh_dazz_open((d.dir + "/" + d.root + "." + std::to_string(block) + "." + d.ext).c_str(), &blk)) return "mask " + name + ": " + dh_last_error();
+    const int32_t first = dh_dazz_first_id(blk) - dh_dazz_first_id(da), nb = dh_dazz_nreads(blk);
+    dh_dazz_close(blk);
+    if (first < 0 || first + nb > ncontigs) return "mask " + name + ": the block lies outside the DB";
+    const std::vector<int64_t> in(ptr);  // (entries 0 .. nb: the block's reads)
+    for (int32_t c = 0; c <= ncontigs; c++) ptr[(size_t)c] = c < first ? 0 : in[(size_t)std::min(c - first, nb)];
+    return "";
+}
+
+// the options both commands take and ignore; an unknown one: the usage and exit 1
+static bool maskops_common_option(const std::string &a, bool *ignored)
+{
+    auto starts = [&](const char *p) { return a.size() > strlen(p) && a.compare(0, strlen(p), p) == 0; };
+    if (a == "-v" || a == "--quiet" || starts("--config=") || starts("-T") || starts("--threads=")) {
+        *ignored = true;
+        return true;
+    }
+    return false;
+}
+
+// `dentist merge-masks` (commands/mergeMasks.d:47-53): the union of the input masks.  Everything that fails behind the options:
+// the library's message and exit 2.
+static int tool_merge_masks(const std::vector<std::string> &args)
+{
+    const std::string usage = "usage: merge-masks [--config=<file>] [-v] [--quiet] [-T<n>] <ref-db> <merged-mask> <input-mask>...";
+    auto fail = [](const std::string &what) {
+        fprintf(stderr, "merge-masks: %s\n", what.c_str());
+        return 2;
+    };
+    std::vector<std::string> pos;
+    bool ignored = false;
+    for (const std::string &a : args) {
+        if (maskops_common_option(a, &ignored)) continue;
+        if (a.size() > 1 && a[0] == '-') die("unknown option " + a + "\n" + usage);
+        pos.push_back(a);
+    }
+    if (pos.size() < 3) die(usage);
+    if (ignored) fprintf(stderr, "merge-masks: --config, -v, --quiet, -T and --threads have no effect here\n");
+    dh_dazz *da = nullptr;
+    if (dh_dazz_open(pos[0].c_str(), &da)) return fail(dh_last_error());
+    const int32_t ncontigs = dh_dazz_nreads(da), nmasks = (int32_t)pos.size() - 2;
+    std::vector<std::vector<int64_t>> ptr((size_t)nmasks);
+    std::vector<std::vector<int32_t>> iv((size_t)nmasks);
+    std::vector<const int64_t *> pp;
+    std::vector<const int32_t *> pi;
+    for (int32_t k = 0; k < nmasks; k++) {
+        const std::string err = read_mask_track(da, pos[0], pos[(size_t)k + 2], ptr[(size_t)k], iv[(size_t)k]);
+        if (!err.empty()) return fail(err);
+        pp.push_back(ptr[(size_t)k].data()), pi.push_back(iv[(size_t)k].data());
+    }
+    dh_ctx *ctx = nullptr;
+    dh_mask_set *res = nullptr;
+    dh_mask_opts o;
+    dh_default_mask_opts(&o);
+    if (dh_ctx_create(0, nullptr, &ctx)) return fail(dh_last_error());
+    if (dh_mask_combine(ctx, pp.data(), pi.data(), nmasks, nullptr, nullptr, dh_dazz_offsets(da), ncontigs, &o, &res)) return fail(dh_last_error());
+    static const int32_t no_iv[2] = {0, 0};
+    if (dh_dazz_write_mask(pos[0].c_str(), pos[1].c_str(), ncontigs, dh_mask_set_ptr(res), dh_mask_set_count(res) > 0 ? dh_mask_set_iv(res) : no_iv))
+        return fail(dh_last_error());
+    dh_mask_set_destroy(res);
+    dh_ctx_destroy(ctx);
+    dh_dazz_close(da);
+    return 0;
+}
+
+// `dentist filter-mask` (commands/filterMask.d:124-159): gaps up to --min-gap-size closed, then intervals below
+// --min-interval-size dropped.  An empty input mask gives an empty mask (the reference indexes an empty array there).
+static int tool_filter_mask(const std::vector<std::string> &args)
+{
+    const std::string usage = "usage: filter-mask [--min-gap-size=<n>] [--min-interval-size=<n>] [--config=<file>] [-v] [--quiet] [-T<n>] "
+                              "<ref-db> <in-mask> <out-mask>";
+    auto fail = [](const std::string &what) {
+        fprintf(stderr, "filter-mask: %s\n", what.c_str());
+        return 2;
+    };
+    std::vector<std::string> pos;
+    bool ignored = false;
+    long long min_gap = 0, min_interval = 0;
+    auto number = [&](const std::string &a, size_t at, long long *out) {
+        char *end = nullptr;
+        *out = strtoll(a.c_str() + at, &end, 10);
+        if (end == a.c_str() + at || *end || *out < 0 || *out > INT32_MAX) die("unknown or malformed option " + a + "\n" + usage);
+    };
+    for (const std::string &a : args) {
+        if (a.compare(0, 15, "--min-gap-size=") == 0)
+            number(a, 15, &min_gap);
+        else if (a.compare(0, 20, "--min-interval-size=") == 0)
+            number(a, 20, &min_interval);
+        else if (maskops_common_option(a, &ignored))
+            continue;
+        else if (a.size() > 1 && a[0] == '-')
+            die("unknown option " + a + "\n" + usage);
+        else
+            pos.push_back(a);
+    }
+    if (pos.size() != 3) die(usage);
+    if (ignored) fprintf(stderr, "filter-mask: --config, -v, --quiet, -T and --threads have no effect here\n");
+    dh_dazz *da = nullptr;
+    if (dh_dazz_open(pos[0].c_str(), &da)) return fail(dh_last_error());
+    const int32_t ncontigs = dh_dazz_nreads(da);
+    std::vector<int64_t> ptr;
+    std::vector<int32_t> iv;
+    const std::string err = read_mask_track(da, pos[0], pos[1], ptr, iv);
+    if (!err.empty()) return fail(err);
+    static const int32_t no_iv[2] = {0, 0};
+    if (ptr[(size_t)ncontigs] == 0) {  // an empty mask, without a device
+        if (dh_dazz_write_mask(pos[0].c_str(), pos[2].c_str(), ncontigs, ptr.data(), no_iv)) return fail(dh_last_error());
+        dh_dazz_close(da);
+        return 0;
+    }
+    dh_ctx *ctx = nullptr;
+    dh_mask_set *res = nullptr;
+    const dh_mask_opts o{1, (int32_t)min_gap, (int32_t)min_interval, 0};
+    const int64_t *pp = ptr.data();
+    const int32_t *pi = iv.data();
+    if (dh_ctx_create(0, nullptr, &ctx)) return fail(dh_last_error());
+    if (dh_mask_combine(ctx, &pp, &pi, 1, nullptr, nullptr, dh_dazz_offsets(da), ncontigs, &o, &res)) return fail(dh_last_error());
+    if (dh_dazz_write_mask(pos[0].c_str(), pos[2].c_str(), ncontigs, dh_mask_set_ptr(res), dh_mask_set_count(res) > 0 ? dh_mask_set_iv(res) : no_iv))
+        return fail(dh_last_error());
+    dh_mask_set_destroy(res);
+    dh_ctx_destroy(ctx);
+    dh_dazz_close(da);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     g_tool = argv[0];
@@ -1914,8 +2058,10 @@ int main(int argc, char **argv)
     if (g_tool == "validate-regions") return tool_validate_regions(args);
     if (g_tool == "collect") return tool_collect(args);
     if (g_tool == "mask-repetitive-regions") return tool_mask_repetitive_regions(args);
+    if (g_tool == "merge-masks") return tool_merge_masks(args);
+    if (g_tool == "filter-mask") return tool_filter_mask(args);
     die("unknown tool (expected fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv "
         "computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index "
-        "chain-local-alignments propagate-mask validate-regions collect mask-repetitive-regions)");
+        "chain-local-alignments propagate-mask validate-regions collect mask-repetitive-regions merge-masks filter-mask)");
     return 1;
 }
