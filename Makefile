@@ -6,7 +6,7 @@ CSRC := dentist_amd/csrc
 LIB := dentist_amd/libdentist_hip.so
 SIM := dentist_amd/sim/libdh_sim.so
 
-DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index chain-local-alignments propagate-mask validate-regions collect mask-repetitive-regions merge-masks filter-mask
+DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index chain-local-alignments propagate-mask validate-regions collect mask-repetitive-regions merge-masks filter-mask check-results
 TOOLS := tools/daligner tools/damapper tools/datander tools/dazz_tools $(addprefix tools/,$(DAZZ_TOOLS))
 
 all: $(LIB) $(SIM) oracle $(TOOLS)
@@ -161,3 +161,13 @@ tests/native/libmaskops_host.so: tests/native/maskops_host.cpp dentist_amd/csrc/
 # the last offset are where this code would overrun
 tests/native/maskops_host_san: tests/native/maskops_host_main.cpp tests/native/maskops_host.cpp dentist_amd/csrc/dh_maskops.h include/dentist_hip.h
 	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/maskops_host_main.cpp tests/native/maskops_host.cpp
+
+# the lane code and the checks of the gap analysis (dentist_amd/csrc/dh_checkgaps.h) compiled for the CPU: test infrastructure
+tests/native/libcheckgaps_host.so: tests/native/checkgaps_host.cpp dentist_amd/csrc/dh_checkgaps.h include/dentist_hip.h
+	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -o $@ $<
+
+# the same harness and a stand-alone main under the host sanitizers (a program of its own: nothing is preloaded); run it once
+# after a change to dh_checkgaps.h -- the last byte of a flank, the byte behind an N-run, the last column of a chunk and the last
+# dust interval of a contig are where this code would overrun
+tests/native/checkgaps_host_san: tests/native/checkgaps_host_main.cpp tests/native/checkgaps_host.cpp dentist_amd/csrc/dh_checkgaps.h include/dentist_hip.h
+	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/checkgaps_host_main.cpp tests/native/checkgaps_host.cpp

@@ -64,6 +64,14 @@ INSERTION_DTYPE = np.dtype([(n, "<i4") for n in (
     "right_abpos", "ins_begin", "ins_end", "comp", "cons_len", "left_diffs", "right_diffs", "join")]
     + [("cons_off", "<i8"), ("contig_right", "<i4"), ("pad", "<i4")])
 
+# dh_contig_mapping / dh_gap_summary (dh_check_gaps)
+CONTIG_MAPPING_DTYPE = np.dtype([("ref_contig", "<i4"), ("ref_begin", "<i4"), ("ref_end", "<i4"), ("ref_contig_length", "<i4"),
+                                 ("query_contig", "<i4"), ("duplicate", "<i4"), ("complement", "<i4"), ("alignment_error", "<f4")])
+GAP_SUMMARY_DTYPE = np.dtype([(f, "<i4") for f in (
+    "state", "gap_length", "lhs_map", "rhs_map", "align_status", "complement", "true_contig", "true_begin", "true_end",
+    "result_begin_contig", "result_begin", "result_end_contig", "result_end", "col_begin", "col_end", "reference_length",
+    "query_length", "matches", "dust_ops", "dust_matches", "none_dust_ops", "none_dust_matches")])
+GAP_STATES = ("unkown", "broken", "unclosed", "partiallyClosed", "closed", "ignored")
 # dh_exact_hit (32 bytes): one exact occurrence of a query (complement 1: of its reverse complement) in a reference record
 EXACT_HIT_DTYPE = np.dtype([("query", "<i4"), ("ref", "<i4"), ("begin", "<i8"), ("end", "<i8"), ("complement", "<i4"),
                             ("pad", "<i4")])
@@ -130,6 +138,8 @@ SYMBOLS = [
     "dh_repeat_result_improper_units", "dh_repeat_result_tier_contigs", "dh_repeat_result_groups",
     "dh_default_mask_opts", "dh_mask_combine", "dh_la_tandem_mask", "dh_mask_set_destroy", "dh_mask_set_ptr", "dh_mask_set_iv",
     "dh_mask_set_count", "dh_mask_set_events", "dh_mask_set_sort_passes", "dh_mask_set_groups",
+    "dh_check_gaps", "dh_gap_report_destroy", "dh_gap_report_count", "dh_gap_report_summaries", "dh_gap_report_paths",
+    "dh_gap_report_aligned", "dh_gap_report_groups",
 ]
 
 _LIB = None
@@ -336,6 +346,15 @@ def lib():
     for name in ("count", "events", "sort_passes", "groups"):
         getattr(L, "dh_mask_set_" + name).argtypes = [vp]
         getattr(L, "dh_mask_set_" + name).restype = i64
+    L.dh_check_gaps.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, i32, ctypes.POINTER(vp)]
+    L.dh_gap_report_destroy.argtypes = [vp]
+    L.dh_gap_report_destroy.restype = None
+    for name in ("summaries", "paths"):
+        getattr(L, "dh_gap_report_" + name).argtypes = [vp]
+        getattr(L, "dh_gap_report_" + name).restype = vp
+    for name in ("count", "aligned", "groups"):
+        getattr(L, "dh_gap_report_" + name).argtypes = [vp]
+        getattr(L, "dh_gap_report_" + name).restype = i64
     _LIB = L
     return L
 
@@ -793,6 +812,35 @@ class Context:
                                      co.ctypes.data, len(co) - 1, ctypes.byref(o), ctypes.byref(h)))
         return MaskSet(h, len(co) - 1)
 
+    def check_gaps(self, true_db, result_db, mapped, maps, result_gap, dust=None, crop=0, scoring=None, first_contig=1, count=None):
+        """dh_check_gaps: the gap analysis of `dentist check-results`.  true_db / result_db: Db objects; mapped: (n_input, 3) rows of
+        (true contig 1-based, begin, end); maps: CONTIG_MAPPING_DTYPE records in any order; result_gap: the N-run behind every result
+        contig; dust: (ptr, iv) in the layout of read_mask, or None; gap i lies behind input contig first_contig + i (1-based); count
+        None: every gap from first_contig on.  Returns a GapReport."""
+        mp = np.ascontiguousarray(mapped, dtype=np.int32).reshape(-1, 3)
+        ma = np.ascontiguousarray(maps, dtype=CONTIG_MAPPING_DTYPE)
+        rg = np.ascontiguousarray(np.concatenate([np.asarray(result_gap, dtype=np.int32).reshape(-1), [0]]), dtype=np.int32)
+        n_res = lib().dh_db_nreads(result_db._h)
+        if len(rg) - 1 != n_res:
+            raise ValueError("result_gap needs one entry per result contig")
+        dp = di = None
+        if dust is not None:
+            dp = np.ascontiguousarray(dust[0], dtype=np.int64)
+            if len(dp) != lib().dh_db_nreads(true_db._h) + 1:
+                raise ValueError("dust[0] needs one entry per true contig and one more")
+            di = np.ascontiguousarray(np.concatenate([np.asarray(dust[1], dtype=np.int32).reshape(-1), [0, 0]]), dtype=np.int32)
+            if len(dp) and 2 * int(dp.max()) > len(di) - 2:
+                raise ValueError("the dust mask's ptr lies behind the end of its intervals")
+        sc = _scoring(scoring)
+        if count is None:
+            count = max(len(mp) - int(first_contig) + 1, 0)
+        h = ctypes.c_void_p()
+        _check(lib().dh_check_gaps(self._h, true_db._h, result_db._h, mp.ctypes.data if len(mp) else None, len(mp),
+                                   ma.ctypes.data if len(ma) else None, len(ma), rg.ctypes.data, dp.ctypes.data if dp is not None else None,
+                                   di.ctypes.data if di is not None else None, int(crop), sc.ctypes.data if sc is not None else None,
+                                   int(first_contig), int(count), ctypes.byref(h)))
+        return GapReport(h)
+
     def tandem_mask(self, las, read_off, first_read=0, min_len=500):
         """dh_la_tandem_mask: TANmask's rule on the device -- the union of [min(abpos, bbpos), max(aepos, bepos)) over the
         records with aread == bread on the same strand that are at least min_len long, per read aread - first_read.  Returns
@@ -870,6 +918,64 @@ class EditPaths:
                 self._h = None
         except Exception:
             pass
+
+
+class GapReport:
+    """Result of Context.check_gaps, copied out of the library: summaries (GAP_SUMMARY_DTYPE, one per gap), identity (float64: matches
+    over kept columns, NaN at zero columns), the uncropped ops of gap i at ops[op_off[i]:op_off[i + 1]] (empty unless align_status is
+    1), score per gap, and the counters aligned (pairs handed to the aligner) and groups (its launch groups)."""
+
+    def __init__(self, h):
+        L = lib()
+        try:
+            n = int(L.dh_gap_report_count(h))
+            self.summaries = np.zeros(n, dtype=GAP_SUMMARY_DTYPE)
+            if n:
+                ctypes.memmove(self.summaries.ctypes.data, L.dh_gap_report_summaries(h), n * GAP_SUMMARY_DTYPE.itemsize)
+            p = L.dh_gap_report_paths(h)
+            self.op_off = np.zeros(n + 1, dtype=np.int64)
+            ctypes.memmove(self.op_off.ctypes.data, L.dh_edit_paths_op_off(p), 8 * (n + 1))
+            self.ops = np.zeros(int(self.op_off[-1]), dtype=np.uint8)
+            if len(self.ops):
+                ctypes.memmove(self.ops.ctypes.data, L.dh_edit_paths_ops(p), len(self.ops))
+            self.score = np.zeros(n, dtype=np.int32)
+            if n:
+                ctypes.memmove(self.score.ctypes.data, L.dh_edit_paths_score(p), 4 * n)
+            self.aligned, self.groups = int(L.dh_gap_report_aligned(h)), int(L.dh_gap_report_groups(h))
+        finally:
+            L.dh_gap_report_destroy(h)
+        cols = (self.summaries["col_end"] - self.summaries["col_begin"]).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.identity = np.where(cols > 0, self.summaries["matches"] / cols, np.nan)
+
+    def __len__(self):
+        return len(self.summaries)
+
+    def ops_of(self, i):
+        return self.ops[self.op_off[i]:self.op_off[i + 1]]
+
+
+def contig_mappings(ctx, ref_seqs, result_seqs, crop_alignment=0, crop_ambiguous=0):
+    """findReferenceContigs / findPerfectAlignmentsChunk of `dentist check-results` (commands/checkResults.d:399-565) over
+    Context.exact_locate: the input contigs ref_seqs cropped by crop_alignment on both sides are searched in result_seqs on both
+    strands, every hit is a mapping; an input contig is a duplicate when, cropped by crop_ambiguous, it occurs in another input
+    contig.  A contig that the crop leaves empty is not searched.  Returns CONTIG_MAPPING_DTYPE records sorted by input contig."""
+    def cropped(crop):
+        ids = [i for i, s in enumerate(ref_seqs) if len(s) > 2 * crop]
+        return ids, [np.asarray(ref_seqs[i], dtype=np.uint8)[crop:len(ref_seqs[i]) - crop] for i in ids]
+    ids, qs = cropped(int(crop_ambiguous))
+    dup = set()
+    if qs:
+        for h in ctx.exact_locate(ref_seqs, qs, True):
+            if int(h["ref"]) != ids[int(h["query"])]:
+                dup.add(ids[int(h["query"])])
+    ids, qs = cropped(int(crop_alignment))
+    hits = ctx.exact_locate(result_seqs, qs, True) if qs else np.zeros(0, EXACT_HIT_DTYPE)
+    out = np.zeros(len(hits), dtype=CONTIG_MAPPING_DTYPE)
+    for k, h in enumerate(hits):
+        q = ids[int(h["query"])]
+        out[k] = (int(h["ref"]) + 1, int(h["begin"]), int(h["end"]), len(result_seqs[int(h["ref"])]), q + 1, int(q in dup), int(h["complement"]), 0.0)
+    return out[np.argsort(out["query_contig"], kind="stable")]
 
 
 class Chains:

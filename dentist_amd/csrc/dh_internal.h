@@ -168,6 +168,11 @@ enum DhSlot : int {
     // mask algebra (dh_mask_combine, dh_la_tandem_mask, dh_maskops.cpp): every buffer of a launch group, carved from one request
     // (the input, the keys twice, the scanned words, the boundaries, the runs in two stages, the output)
     SLOT_MO_WORK,
+    // gap analysis (dh_check_gaps, dh_checkgaps.cpp): all live for one call.  SLOT_CG_IN is the uploaded input (mapped triples, the
+    // mappings sorted by input contig, the N-runs, the dust mask), SLOT_CG_SUM the summaries, SLOT_CG_ROFF / QOFF the pair lengths and
+    // then their scans, SLOT_CG_SUMS the scans' block sums, SLOT_CG_REF / QRY the gathered sequences in the aligner's padded layout,
+    // SLOT_CG_OPS the ops of the aligned pairs with their offsets in front
+    SLOT_CG_IN, SLOT_CG_SUM, SLOT_CG_ROFF, SLOT_CG_QOFF, SLOT_CG_SUMS, SLOT_CG_REF, SLOT_CG_QRY, SLOT_CG_OPS,
     DH_SLOT_COUNT
 };
 // The words of SLOT_STATUS (DH_STW_COUNT x int32), one buffer with three users.  All of them run on the context's stream:
@@ -432,6 +437,10 @@ struct DhNwPairOut {
 };
 int dh_nw_run_pairs(dh_ctx *ctx, const uint8_t *d_ref, const uint8_t *d_qry, const DhNwSeq *seq, const std::vector<int64_t> &todo,
                     int32_t fs, std::vector<DhNwPairOut> &out, std::vector<uint8_t> &stage);
+// dh_nwa.cpp: the same for the affine-gap alignment (dh_nw_affine_batch's chunks, dh_check_gaps' gathered pairs); sc NULL: the
+// default; *groups (or NULL) counts the launch groups
+int dh_nwa_run_pairs(dh_ctx *ctx, const uint8_t *d_ref, const uint8_t *d_qry, const DhNwSeq *seq, const std::vector<int64_t> &todo,
+                     const dh_nw_scoring *sc, std::vector<DhNwPairOut> &out, std::vector<uint8_t> &stage, int64_t *groups);
 // dh_editpath.cpp: validation of one record as dh_la_edit_paths validates it (its tiles are appended to `tiles`), and the tiles [t0, t1) of `tiles` through the edit-path kernels with their
 // ops left on the device, tile after tile (*d_ops; NULL when there is none): res[t] = nops / score per tile
 struct EpTile;

@@ -8,6 +8,7 @@
 // applies nwa::accepted to the cost it reports, and the pairs that fail run again, together, at twice the half-width -- in
 // launch groups bounded by the same knob, one launch per kernel class -- until the band would exceed NWA_MAX_W columns:
 // those get DH_NW_BAND_EXCEEDED.  k_edit_compact (dh_editpath.hip) puts the ops of a group in path order.
+// dh_nwa_run_pairs is the same protocol for a caller whose pairs are on the device already (dh_check_gaps, dh_checkgaps.cpp).
 #include "dh_host.h"
 
 #include <stdio.h>
@@ -45,19 +46,16 @@ struct Job {
     int64_t words;  // decision words
 };
 
-struct PairOut {
-    int64_t at = 0;  // first op in the staging vector
-    int32_t nops = 0, score = 0, status = DH_NW_OK;
-};
+using PairOut = DhNwPairOut;
 
 struct NwaRun {
     dh_ctx *ctx;
-    const int64_t *ref_off, *qry_off;
-    int64_t p0;  // first pair of the chunk: its sequences start at NW_SEQ_PAD of the device buffers
+    const DhNwSeq *seq;  // by pair: where its sequences start in the device buffers, and their lengths
     const uint8_t *d_ref, *d_qry;
     NwaCost cost;
     std::vector<PairOut> *out;
     std::vector<uint8_t> *stage;
+    int64_t *groups;  // launch groups run (NULL: not counted)
 };
 
 // jobs [j0, j1) (sorted by class) as one launch group; the rejected ones are appended to `again`
@@ -66,15 +64,16 @@ int run_launch(const NwaRun &r, const std::vector<Job> &jobs, size_t j0, size_t 
     dh_ctx *ctx = r.ctx;
     hipStream_t st = ctx->stream;
     const size_t n = j1 - j0;
+    if (r.groups) ++*r.groups;
     std::vector<NwPair> pairs(n);
     int64_t dm_words = 0, ow_words = 0;
     for (size_t k = 0; k < n; k++) {
         const Job &jb = jobs[j0 + k];
         NwPair &p = pairs[k];
-        p.roff = NW_SEQ_PAD + r.ref_off[jb.pair] - r.ref_off[r.p0];
-        p.qoff = NW_SEQ_PAD + r.qry_off[jb.pair] - r.qry_off[r.p0];
-        p.rl = (int32_t)(r.ref_off[jb.pair + 1] - r.ref_off[jb.pair]);
-        p.ql = (int32_t)(r.qry_off[jb.pair + 1] - r.qry_off[jb.pair]);
+        p.roff = r.seq[jb.pair].roff;
+        p.qoff = r.seq[jb.pair].qoff;
+        p.rl = r.seq[jb.pair].rl;
+        p.ql = r.seq[jb.pair].ql;
         p.lo = jb.b.lo;
         p.hi = jb.b.hi;
         p.dm_off = dm_words;
@@ -142,18 +141,11 @@ bool plan(int32_t rl, int32_t ql, int64_t w, Job &jb)
     return true;
 }
 
-// the device pairs `todo` of chunk [p0, p1): attempts at growing half-widths until every pair is accepted or given up
-int run_chunk(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off, const uint8_t *qry, const int64_t *qry_off, int64_t p0,
-              int64_t p1, const std::vector<int64_t> &todo, const NwaCost &cost, std::vector<PairOut> &out, std::vector<uint8_t> &stage)
+// the pairs `todo` whose sequences are on the device: attempts at growing half-widths until every pair is accepted or given up
+int run_pairs(const NwaRun &r, const std::vector<int64_t> &todo)
 {
-    hipStream_t st = ctx->stream;
-    const int64_t rbytes = ref_off[p1] - ref_off[p0], qbytes = qry_off[p1] - qry_off[p0];
-    uint8_t *d_ref, *d_qry;
-    if (int rc = dh_scr(ctx, SLOT_NWA_REF, (size_t)rbytes + 2 * NW_SEQ_PAD, &d_ref)) return rc;
-    if (int rc = dh_scr(ctx, SLOT_NWA_QRY, (size_t)qbytes + 2 * NW_SEQ_PAD, &d_qry)) return rc;
-    if (rbytes) HIPCHK(hipMemcpyAsync(d_ref + NW_SEQ_PAD, ref + ref_off[p0], (size_t)rbytes, hipMemcpyHostToDevice, st));
-    if (qbytes) HIPCHK(hipMemcpyAsync(d_qry + NW_SEQ_PAD, qry + qry_off[p0], (size_t)qbytes, hipMemcpyHostToDevice, st));
-    const NwaRun r{ctx, ref_off, qry_off, p0, d_ref, d_qry, cost, &out, &stage};
+    const DhNwSeq *seq = r.seq;
+    std::vector<PairOut> &out = *r.out;
     const int64_t budget = nwa_budget_words(), w0 = nwa_first_w();
     std::vector<Job> jobs, again;
     for (int64_t p : todo) {
@@ -165,7 +157,7 @@ int run_chunk(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off, const uin
     while (!again.empty()) {
         jobs.clear();
         for (Job jb : again) {
-            const int32_t rl = (int32_t)(ref_off[jb.pair + 1] - ref_off[jb.pair]), ql = (int32_t)(qry_off[jb.pair + 1] - qry_off[jb.pair]);
+            const int32_t rl = seq[jb.pair].rl, ql = seq[jb.pair].ql;
             const int64_t w = nwa::next_w(rl, ql, jb.w, w0);
             if (w < 0) {
                 PairOut &o = out[(size_t)jb.pair];
@@ -188,7 +180,40 @@ int run_chunk(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off, const uin
     return DH_OK;
 }
 
+// the device pairs `todo` of chunk [p0, p1): their bases go up as one range, `seq` (one entry per pair of the call) gets theirs
+int run_chunk(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off, const uint8_t *qry, const int64_t *qry_off, int64_t p0,
+              int64_t p1, const std::vector<int64_t> &todo, const NwaCost &cost, std::vector<DhNwSeq> &seq, std::vector<PairOut> &out,
+              std::vector<uint8_t> &stage)
+{
+    hipStream_t st = ctx->stream;
+    const int64_t rbytes = ref_off[p1] - ref_off[p0], qbytes = qry_off[p1] - qry_off[p0];
+    uint8_t *d_ref, *d_qry;
+    if (int rc = dh_scr(ctx, SLOT_NWA_REF, (size_t)rbytes + 2 * NW_SEQ_PAD, &d_ref)) return rc;
+    if (int rc = dh_scr(ctx, SLOT_NWA_QRY, (size_t)qbytes + 2 * NW_SEQ_PAD, &d_qry)) return rc;
+    if (rbytes) HIPCHK(hipMemcpyAsync(d_ref + NW_SEQ_PAD, ref + ref_off[p0], (size_t)rbytes, hipMemcpyHostToDevice, st));
+    if (qbytes) HIPCHK(hipMemcpyAsync(d_qry + NW_SEQ_PAD, qry + qry_off[p0], (size_t)qbytes, hipMemcpyHostToDevice, st));
+    for (int64_t p = p0; p < p1; p++)
+        seq[(size_t)p] = DhNwSeq{NW_SEQ_PAD + ref_off[p] - ref_off[p0], NW_SEQ_PAD + qry_off[p] - qry_off[p0], (int32_t)(ref_off[p + 1] - ref_off[p]),
+                                 (int32_t)(qry_off[p + 1] - qry_off[p])};
+    return run_pairs(NwaRun{ctx, seq.data(), d_ref, d_qry, cost, &out, &stage, nullptr}, todo);
+}
+
 }  // namespace
+
+// The same protocol on pairs whose sequences the caller left on the device (dh_check_gaps): d_ref / d_qry carry NW_SEQ_PAD bytes in
+// front of the first and behind the last sequence, seq[p] says where pair p lies; sc is a scoring dh_nw_affine_batch accepts and
+// no sequence is empty or longer than DH_NWA_MAX_LEN (DH_EINVAL otherwise).  The ops of the accepted pairs are appended to `stage`.
+int dh_nwa_run_pairs(dh_ctx *ctx, const uint8_t *d_ref, const uint8_t *d_qry, const DhNwSeq *seq, const std::vector<int64_t> &todo,
+                     const dh_nw_scoring *sc, std::vector<DhNwPairOut> &out, std::vector<uint8_t> &stage, int64_t *groups)
+{
+    NwaCost cost;
+    if (!sc) sc = &kDefaultScoring;
+    if (!nwa::costs(sc->match, sc->mismatch, sc->gap_open, sc->gap_extend, cost)) return dh_fail(DH_EINVAL, "dh_nwa_run_pairs: scoring refused");
+    for (int64_t p : todo)
+        if (seq[p].rl < 1 || seq[p].ql < 1 || seq[p].rl > NWA_MAX_LEN || seq[p].ql > NWA_MAX_LEN)
+            return dh_fail(DH_EINVAL, "dh_nwa_run_pairs: a pair is empty or too long");
+    return run_pairs(NwaRun{ctx, seq, d_ref, d_qry, cost, &out, &stage, groups}, todo);
+}
 
 extern "C" int dh_nw_affine_batch(dh_ctx *ctx, const uint8_t *ref, const int64_t *ref_off, const uint8_t *qry, const int64_t *qry_off,
                                   int64_t n, const dh_nw_scoring *sc, dh_edit_paths **out, int32_t *status)
@@ -219,6 +244,7 @@ extern "C" int dh_nw_affine_batch(dh_ctx *ctx, const uint8_t *ref, const int64_t
     if (n > 0 && ((ref_off[n] > ref_off[0] && !ref) || (qry_off[n] > qry_off[0] && !qry)))
         return dh_fail(DH_EINVAL, "dh_nw_affine_batch: sequences are NULL");
     std::vector<PairOut> po((size_t)n);
+    std::vector<DhNwSeq> seq((size_t)n);
     std::vector<uint8_t> stage;
     // ---- chunks of consecutive pairs: the decision words of the first attempts within the budget, 256 MB of bases at most (those of
     // pairs with an empty side included: a chunk's bases are uploaded as one range)
@@ -243,7 +269,7 @@ extern "C" int dh_nw_affine_batch(dh_ctx *ctx, const uint8_t *ref, const int64_t
             HIPCHK(hipSetDevice(ctx->device));
             device_set = true;
         }
-        if (int rc = run_chunk(ctx, ref, ref_off, qry, qry_off, p0, p1, todo, cost, po, stage)) return rc;
+        if (int rc = run_chunk(ctx, ref, ref_off, qry, qry_off, p0, p1, todo, cost, seq, po, stage)) return rc;
     }
     // ---- the result in pair order; a pair with an empty side is one gap
     std::unique_ptr<dh_edit_paths> p(new dh_edit_paths);

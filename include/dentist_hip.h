@@ -1199,6 +1199,84 @@ int64_t dh_mask_set_events(const dh_mask_set *s);          /* keys written (test
 int64_t dh_mask_set_sort_passes(const dh_mask_set *s);     /* radix passes (tests) */
 int64_t dh_mask_set_groups(const dh_mask_set *s);          /* launch groups (tests) */
 
+/* ---- gap analysis of `dentist check-results` on the device (commands/checkResults.d: analyzeGaps :822-907, getGapState and
+ *      isGap* :909-982, getInsertionMapping :984-1009, inputGapSize :1037-1046, computeInsertionAlignment :1270-1291,
+ *      resultSubseqString :1355-1385, addDustAnalysis :1387-1462, StretcherAlignment.cropReference :1986-2011, the early return
+ *      of stretcher :2081-2089): every gap of a batch of input contigs classified, and the inserted sequence of every closed or
+ *      partially closed gap aligned to the true one, in one call.  tools/check-results is the drop-in of a subset of the
+ *      command.  Kernels: csrc/dh_checkgaps.hip; lane code: csrc/dh_checkgaps.h.
+ *   Input.  true_db / result_db: the true assembly and the result (contig c of the reference is sequence c - 1).  mapped: n_input
+ *      triples (true contig 1-based or 0, begin, end), the mapped interval of every input contig.  maps: nmaps mappings in any
+ *      order, the mappings of the input contigs cropped by `crop` on both sides.  result_gap[c - 1]: the N-run behind result
+ *      contig c (0: none).  dust_ptr (true contigs + 1) / dust_iv: the dust mask in the layout of dh_dazz_read_mask, both NULL
+ *      for none.  scoring NULL: 5/-4/16/4.  Gap i of the call, 0 <= i < count, lies between input contigs first_contig + i and
+ *      first_contig + i + 1 (1-based, so first_contig >= 1; an input contig behind the last has the empty interval).
+ *   Output, one dh_gap_summary per gap:
+ *      state            the reference's GapState, values 0..5.  DH_GAP_IGNORED unless both mapped intervals lie on the same true
+ *                       contig with id > 0; DH_GAP_UNKOWN unless each side has exactly one mapping with duplicate == 0.
+ *      gap_length       rhs.begin - lhs.end (0 for an ignored gap);  lhs_map / rhs_map: indices into maps, or -1
+ *      align_status     DH_CG_NONE (no attempt: the state is neither closed nor partially closed), DH_CG_OK, DH_CG_EMPTY (a side
+ *                       is empty or the query is all n: the reference returns before it runs stretcher), DH_CG_BAND_EXCEEDED
+ *                       (dh_nw_affine_batch's), DH_CG_TOO_LONG (a side over DH_NWA_MAX_LEN).  The last two keep the state; no
+ *                       alignment is invented.
+ *      complement       lhs mapping's; the query was reverse-complemented (n stays n)
+ *      true_contig, true_begin, true_end    [lhs.end - crop, rhs.begin + crop) of the true contig
+ *      result_begin_contig, result_begin, result_end_contig, result_end    the query: from the end of the left mapping to the
+ *                       begin of the right one, both chosen after the complement swap; across two result contigs the left flank,
+ *                       result_gap times n (code 4), the right flank
+ *      col_begin, col_end   the columns cropReference keeps (crop 0: all); identity = matches / (col_end - col_begin)
+ *      reference_length, query_length   crop 0: the bases of both sides (n included); crop > 0: the bases (codes 0..3) inside the
+ *                       kept columns -- 0 when there is no alignment, as cropReference of an alignment without lines gives
+ *      matches          '|' columns among the kept
+ *      dust_ops, dust_matches, none_dust_ops, none_dust_matches   DH_GAP_CLOSED with a dust mask and DH_CG_OK only, else 0
+ *      dh_gap_report_paths: a dh_edit_paths of one entry per gap (every accessor and formatter applies) with the uncropped ops
+ *      of the DH_CG_OK gaps; score = the alignment score.
+ *   Refusals, made on the host before anything is launched, naming the lowest offender: DH_EINVAL "bad argument" for a NULL
+ *      pointer, a negative count or crop; first_contig < 1 or first_contig + count - 1 > n_input; a mapped interval with a contig id
+ *      out of range, outside its contig, or -- a deviation: the reference's mask would merge them silently -- not behind the
+ *      interval before it on the same true contig with at least one base between them; a true interval
+ *      [lhs.end - crop, rhs.begin + crop) outside its contig; a mapping with an id out of range, outside its result contig, or
+ *      whose ref_contig_length is not the contig's; a dust mask that is not sorted and disjoint or leaves its contig; a scoring
+ *      dh_nw_affine_batch refuses.  count == 0: an empty report, no launch.  DH_EOVERFLOW for 2^30 bases of pairs or more is the one
+ *      refusal behind a launch: the pair lengths are known once k_cg_bind has run. */
+typedef struct {
+    int32_t ref_contig, ref_begin, ref_end; /* ContigMapping.reference: result contig (1-based), [begin, end) */
+    int32_t ref_contig_length;
+    int32_t query_contig;                   /* input contig, 1-based */
+    int32_t duplicate, complement;
+    float alignment_error;                  /* carried, not read */
+} dh_contig_mapping;                        /* 32 bytes */
+typedef struct {
+    int32_t state, gap_length, lhs_map, rhs_map, align_status, complement;
+    int32_t true_contig, true_begin, true_end;
+    int32_t result_begin_contig, result_begin, result_end_contig, result_end;
+    int32_t col_begin, col_end;
+    int32_t reference_length, query_length, matches;
+    int32_t dust_ops, dust_matches, none_dust_ops, none_dust_matches;
+} dh_gap_summary;                           /* 88 bytes */
+#define DH_GAP_UNKOWN 0
+#define DH_GAP_BROKEN 1
+#define DH_GAP_UNCLOSED 2
+#define DH_GAP_PARTIALLY_CLOSED 3
+#define DH_GAP_CLOSED 4
+#define DH_GAP_IGNORED 5
+#define DH_CG_NONE 0
+#define DH_CG_OK 1
+#define DH_CG_EMPTY 2
+#define DH_CG_BAND_EXCEEDED 3
+#define DH_CG_TOO_LONG 4
+typedef struct dh_gap_report dh_gap_report;
+int dh_check_gaps(dh_ctx *ctx, dh_db *true_db, dh_db *result_db, const int32_t *mapped /* 3 x n_input */, int32_t n_input,
+                  const dh_contig_mapping *maps, int32_t nmaps, const int32_t *result_gap /* per result contig */,
+                  const int64_t *dust_ptr, const int32_t *dust_iv, int32_t crop, const dh_nw_scoring *scoring /* NULL: the default */,
+                  int32_t first_contig, int32_t count, dh_gap_report **out);
+void dh_gap_report_destroy(dh_gap_report *r);
+int64_t dh_gap_report_count(const dh_gap_report *r);
+const dh_gap_summary *dh_gap_report_summaries(const dh_gap_report *r);
+const dh_edit_paths *dh_gap_report_paths(const dh_gap_report *r); /* owned by the report */
+int64_t dh_gap_report_aligned(const dh_gap_report *r);            /* pairs handed to the aligner (tests) */
+int64_t dh_gap_report_groups(const dh_gap_report *r);             /* the aligner's launch groups (tests) */
+
 /* ---- gap-closed assembly writer (host only): the linear-scaffold subset of `dentist output`
  *      (source/dentist/commands/output.d:743-925): header "<id>\tscaffold-<first contig id>", contig
  *      slices lower case, insertions upper case (highlight != 0), unclosed gaps as 'n' runs, lines

@@ -71,6 +71,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <string>
 #include <vector>
 
@@ -2021,6 +2022,253 @@ static int tool_filter_mask(const std::vector<std::string> &args)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- check-results
+// `dentist check-results` (commands/checkResults.d), the subset tools/README.md states: the input contigs are placed in the result
+// by exact search (dh_exact_locate, findReferenceContigs :399-565), every gap goes through dh_check_gaps, and the stats that need
+// only the mask, the DB lengths, the mappings and the summaries are printed.  Everything that fails behind the options: the
+// library's message and exit 2.
+static int tool_check_results(const std::vector<std::string> &args)
+{
+    const std::string usage = "usage: check-results [--crop-alignment=<n>] [--crop-ambiguous=<n>] [--dust=<mask>] [--gap-details=<json>] "
+                              "[--gap-details-context=0] [--json] [--config=<file>] [-v] [--quiet] [-T<n>] "
+                              "<true-assembly> <mapped-regions-mask> <reference> <result>";
+    auto fail = [](const std::string &what) {
+        fprintf(stderr, "check-results: %s\n", what.c_str());
+        return 2;
+    };
+    std::vector<std::string> pos;
+    bool ignored = false, json = false, dust_given = false;
+    long long crop = 0, crop_amb = 100, context = 0;
+    std::string dust_name = "dust", details;
+    auto number = [&](const std::string &a, size_t at, long long *out) {
+        char *end = nullptr;
+        *out = strtoll(a.c_str() + at, &end, 10);
+        if (end == a.c_str() + at || *end || *out < 0 || *out > INT32_MAX) die("unknown or malformed option " + a + "\n" + usage);
+    };
+    for (const std::string &a : args) {
+        if (a.compare(0, 17, "--crop-alignment=") == 0)
+            number(a, 17, &crop);
+        else if (a.compare(0, 17, "--crop-ambiguous=") == 0)
+            number(a, 17, &crop_amb);
+        else if (a.compare(0, 22, "--gap-details-context=") == 0)
+            number(a, 22, &context);
+        else if (a.compare(0, 7, "--dust=") == 0 && a.size() > 7)
+            dust_name = a.substr(7), dust_given = true;
+        else if (a.compare(0, 14, "--gap-details=") == 0 && a.size() > 14)
+            details = a.substr(14);
+        else if (a == "--json" || a == "-j")
+            json = true;
+        else if (maskops_common_option(a, &ignored))
+            continue;
+        else if (a.size() > 1 && a[0] == '-')
+            die("unknown option " + a + "\n" + usage);
+        else
+            pos.push_back(a);
+    }
+    if (pos.size() != 4) die(usage);
+    if (crop > crop_amb) die("--crop-alignment must be <= --crop-ambiguous\n" + usage);
+    if (context != 0) die("--gap-details-context: only 0 is served (the sequence is null)\n" + usage);
+    if (ignored) fprintf(stderr, "check-results: --config, -v, --quiet, -T and --threads have no effect here\n");
+    dh_dazz *dt = nullptr, *dr = nullptr, *ds = nullptr;
+    if (dh_dazz_open(pos[0].c_str(), &dt) || dh_dazz_open(pos[2].c_str(), &dr) || dh_dazz_open(pos[3].c_str(), &ds)) return fail(dh_last_error());
+    const int32_t n_true = dh_dazz_nreads(dt), n_ref = dh_dazz_nreads(dr), n_res = dh_dazz_nreads(ds);
+    const int64_t *toff = dh_dazz_offsets(dt), *qoff = dh_dazz_offsets(dr), *soff = dh_dazz_offsets(ds);
+    // 2 crop < cutoff: the cutoff of the reference DB's stub, else its shortest contig
+    long long cutoff = -1;
+    {
+        std::ifstream stub(pos[2]);
+        std::string line;
+        while (std::getline(stub, line)) {
+            const size_t at = line.find("cutoff = ");
+            if (at != std::string::npos) cutoff = atoll(line.c_str() + at + 9);
+        }
+        if (cutoff < 0)
+            for (int32_t c = 0; c < n_ref; c++) cutoff = cutoff < 0 ? qoff[c + 1] - qoff[c] : std::min<long long>(cutoff, qoff[c + 1] - qoff[c]);
+    }
+    if (n_ref > 0 && (2 * crop >= cutoff || 2 * crop_amb >= cutoff))
+        return fail("--crop-alignment and --crop-ambiguous: twice the crop must stay below the contig cutoff of " + std::to_string(cutoff));
+    // ---- the mapped intervals are the input contigs, in order
+    std::vector<int64_t> mptr, dptr;
+    std::vector<int32_t> miv, div;
+    std::string err = read_mask_track(dt, pos[0], pos[1], mptr, miv);
+    if (!err.empty()) return fail(err);
+    std::vector<int32_t> mapped;
+    for (int32_t t = 0; t < n_true; t++)
+        for (int64_t k = mptr[(size_t)t]; k < mptr[(size_t)t + 1]; k++) mapped.insert(mapped.end(), {t + 1, miv[(size_t)(2 * k)], miv[(size_t)(2 * k + 1)]});
+    const int32_t n_input = (int32_t)(mapped.size() / 3);
+    if (n_input != n_ref) return fail("the mask " + pos[1] + " has " + std::to_string(n_input) + " intervals, " + pos[2] + " has " + std::to_string(n_ref) + " contigs");
+    bool have_dust = true;
+    err = read_mask_track(dt, pos[0], dust_name, dptr, div);
+    if (!err.empty()) {
+        if (dust_given) return fail(err);
+        have_dust = false;  // (the default track is used when it is there)
+    }
+    std::vector<int32_t> result_gap((size_t)n_res + 1, 0);
+    for (int32_t c = 0; c + 1 < n_res; c++)
+        if (dh_dazz_origin(ds)[c + 1] > dh_dazz_origin(ds)[c] && strcmp(dh_dazz_header(ds, c), dh_dazz_header(ds, c + 1)) == 0)
+            result_gap[(size_t)c] = dh_dazz_fpulse(ds)[c + 1] - (int32_t)(dh_dazz_fpulse(ds)[c] + (soff[c + 1] - soff[c]));
+    dh_ctx *ctx = nullptr;
+    if (dh_ctx_create(0, nullptr, &ctx)) return fail(dh_last_error());
+    // ---- findReferenceContigs: duplicates by the self search at --crop-ambiguous, mappings by the search in the result
+    auto cropped = [&](long long by, std::vector<uint8_t> &b, std::vector<int64_t> &o) {
+        o.assign(1, 0);
+        for (int32_t c = 0; c < n_ref; c++) {
+            const int64_t len = qoff[c + 1] - qoff[c];
+            if (len > 2 * by) b.insert(b.end(), dh_dazz_bases(dr) + qoff[c] + by, dh_dazz_bases(dr) + qoff[c + 1] - by);
+            o.push_back((int64_t)b.size());
+        }
+    };
+    std::vector<uint8_t> qb;
+    std::vector<int64_t> qo;
+    std::vector<char> dup((size_t)n_ref + 1, 0);
+    dh_exact_hits *hits = nullptr;
+    cropped(crop_amb, qb, qo);
+    if (dh_exact_locate(ctx, dh_dazz_bases(dr), qoff, n_ref, qb.data(), qo.data(), n_ref, 1, &hits)) return fail(dh_last_error());
+    for (int64_t k = 0; k < dh_exact_hits_count(hits); k++) {
+        const dh_exact_hit &h = dh_exact_hits_records(hits)[k];
+        if (h.ref != h.query && qo[(size_t)h.query + 1] > qo[(size_t)h.query]) dup[(size_t)h.query] = 1;
+    }
+    dh_exact_hits_destroy(hits);
+    qb.clear();
+    cropped(crop, qb, qo);
+    if (dh_exact_locate(ctx, dh_dazz_bases(ds), soff, n_res, qb.data(), qo.data(), n_ref, 1, &hits)) return fail(dh_last_error());
+    std::vector<dh_contig_mapping> maps;
+    for (int64_t k = 0; k < dh_exact_hits_count(hits); k++) {
+        const dh_exact_hit &h = dh_exact_hits_records(hits)[k];
+        if (qo[(size_t)h.query + 1] == qo[(size_t)h.query]) continue;  // (a contig the crop leaves empty is not searched)
+        maps.push_back(dh_contig_mapping{h.ref + 1, (int32_t)h.begin, (int32_t)h.end, (int32_t)(soff[h.ref + 1] - soff[h.ref]), h.query + 1,
+                                         dup[(size_t)h.query], h.complement, 0.0f});
+    }
+    dh_exact_hits_destroy(hits);
+    // ---- the gaps
+    dh_db *T = nullptr, *S = nullptr;
+    if (dh_db_create(ctx, dh_dazz_bases(dt), toff, n_true, nullptr, &T) || dh_db_create(ctx, dh_dazz_bases(ds), soff, n_res, nullptr, &S))
+        return fail(dh_last_error());
+    dh_gap_report *rep = nullptr;
+    if (dh_check_gaps(ctx, T, S, mapped.data(), n_input, maps.data(), (int32_t)maps.size(), result_gap.data(), have_dust ? dptr.data() : nullptr,
+                      have_dust ? div.data() : nullptr, (int32_t)crop, nullptr, 1, n_input, &rep))
+        return fail(dh_last_error());
+    const dh_gap_summary *gs = dh_gap_report_summaries(rep);
+    const dh_edit_paths *paths = dh_gap_report_paths(rep);
+    auto ratio = [](double a, double b) { return b > 0 ? a / b : std::nan(""); };
+    auto num = [](double x) {  // (NaN has no JSON text: null)
+        char buf[40];
+        snprintf(buf, sizeof(buf), "%.17g", x);
+        return std::isnan(x) ? std::string("null") : std::string(buf);
+    };
+    static const char *const state_name[6] = {"unkown", "broken", "unclosed", "partiallyClosed", "closed", "ignored"};
+    // ---- --gap-details: one object per gap that is not ignored (writeGapDetailsJson :1203-1239)
+    if (!details.empty()) {
+        FILE *f = fopen(details.c_str(), "w");
+        if (!f) return fail("cannot write " + details);
+        for (int32_t g = 0; g < n_input; g++) {
+            const dh_gap_summary &s = gs[g];
+            if (s.state == DH_GAP_IGNORED) continue;
+            fprintf(f, "{\"leftContig\":%d,\"rightContig\":%d,\"state\":\"%s\",\"gapLength\":%d,\"details\":", g + 1, g + 2, state_name[s.state], s.gap_length);
+            if (s.state == DH_GAP_CLOSED || s.state == DH_GAP_PARTIALLY_CLOSED) {
+                std::string l[3];
+                if (s.align_status == DH_CG_OK) {
+                    const uint8_t *ops = dh_edit_paths_ops(paths) + dh_edit_paths_op_off(paths)[g];
+                    const uint8_t *rb = dh_dazz_bases(dt) + toff[s.true_contig - 1] + s.true_begin;
+                    // the query as the aligner saw it
+                    std::vector<uint8_t> q;
+                    const uint8_t *sb = dh_dazz_bases(ds);
+                    if (s.result_begin_contig == s.result_end_contig)
+                        q.assign(sb + soff[s.result_begin_contig - 1] + s.result_begin, sb + soff[s.result_begin_contig - 1] + s.result_end);
+                    else {
+                        q.assign(sb + soff[s.result_begin_contig - 1] + s.result_begin, sb + soff[s.result_begin_contig]);
+                        q.insert(q.end(), (size_t)result_gap[(size_t)s.result_begin_contig - 1], (uint8_t)4);
+                        q.insert(q.end(), sb + soff[s.result_end_contig - 1], sb + soff[s.result_end_contig - 1] + s.result_end);
+                    }
+                    if (s.complement) {
+                        std::reverse(q.begin(), q.end());
+                        for (auto &b : q) b = b < 4 ? (uint8_t)(3 - b) : b;
+                    }
+                    int64_t i = 0, j = 0;
+                    for (int32_t k = 0; k < s.col_end; k++) {
+                        const uint8_t op = ops[k];
+                        const char rc_ = op == 2 ? '-' : "acgtn"[std::min<int>(rb[i++], 4)], qc = op == 1 ? '-' : "acgtn"[std::min<int>(q[(size_t)j++], 4)];
+                        if (k < s.col_begin) continue;
+                        l[0] += rc_, l[1] += op == 0 ? '|' : (op == 3 ? '.' : '-'), l[2] += qc;
+                    }
+                }
+                // (cropReference does not carry the complement over: false at crop > 0, as in the reference)
+                fprintf(f, "{\"referenceLength\":%d,\"queryLength\":%d,\"complement\":%s,\"percentIdentity\":%s,\"dustPercentIdentity\":%s,"
+                           "\"noneDustPercentIdentity\":%s,\"alignment\":[\"%s\",\"%s\",\"%s\"]}",
+                        s.reference_length, s.query_length, s.complement && crop == 0 ? "true" : "false", num(ratio(s.matches, s.col_end - s.col_begin)).c_str(),
+                        num(ratio(s.dust_matches, s.dust_ops)).c_str(), num(ratio(s.none_dust_matches, s.none_dust_ops)).c_str(), l[0].c_str(), l[1].c_str(),
+                        l[2].c_str());
+            } else
+                fprintf(f, "null");
+            fprintf(f, ",\"sequence\":null}\n");
+        }
+        fclose(f);
+    }
+    // ---- the stats
+    const unsigned long long none = ~0ull;
+    unsigned long long bps_expected = 0, bps_known = 0, bps_result = (unsigned long long)soff[n_res], bps_gaps = 0;
+    std::vector<unsigned long long> scaffolds, inputs, results, gap_len, closed_len;
+    for (int32_t c = 0; c < n_input; c++) {
+        const unsigned long long len = (unsigned long long)(mapped[3 * (size_t)c + 2] - mapped[3 * (size_t)c + 1]);
+        bps_known += len, inputs.push_back(len);
+        if (c == 0 || mapped[3 * (size_t)c] != mapped[3 * (size_t)c - 3]) scaffolds.push_back(0);
+        int32_t first = c;
+        while (first > 0 && mapped[3 * (size_t)first - 3] == mapped[3 * (size_t)c]) first--;
+        scaffolds.back() = (unsigned long long)(mapped[3 * (size_t)c + 2] - mapped[3 * (size_t)first + 1]);
+    }
+    for (unsigned long long x : scaffolds) bps_expected += x;
+    for (int32_t c = 0; c < n_res; c++) results.push_back((unsigned long long)(soff[c + 1] - soff[c]));
+    double weighted = 0;
+    long long correct = 0, closed = 0, partially = 0;
+    for (int32_t g = 0; g < n_input; g++) {
+        const dh_gap_summary &s = gs[g];
+        if (s.state == DH_GAP_IGNORED) continue;
+        const double identity = ratio(s.matches, s.col_end - s.col_begin);
+        bps_gaps += (unsigned long long)s.gap_length, gap_len.push_back((unsigned long long)s.gap_length);
+        weighted += identity * s.gap_length;
+        partially += s.state == DH_GAP_PARTIALLY_CLOSED;
+        if (s.state == DH_GAP_CLOSED) closed++, closed_len.push_back((unsigned long long)s.gap_length), correct += 1.0 <= identity;
+    }
+    std::vector<int32_t> per_contig((size_t)n_input + 1, 0);
+    for (const dh_contig_mapping &m : maps) per_contig[(size_t)m.query_contig] += !m.duplicate;
+    const long long mapped_contigs = std::count(per_contig.begin(), per_contig.end(), 1);
+    auto n50 = [&](std::vector<unsigned long long> v) -> unsigned long long {  // util/math.d N!50 against numBpsExpected
+        std::sort(v.begin(), v.end());
+        double cum = 0;
+        for (size_t k = v.size(); k-- > 0;)
+            if ((cum += (double)v[k]) >= 0.5 * (double)bps_expected) return v[k];
+        return 0;
+    };
+    auto median = [&](std::vector<unsigned long long> v) -> unsigned long long {
+        if (v.empty()) return none;
+        std::sort(v.begin(), v.end());
+        return v.size() > 1 && v.size() % 2 == 0 ? (v[v.size() / 2 - 1] + v[v.size() / 2]) / 2 : v[v.size() / 2];
+    };
+    const double avg_err = bps_gaps ? weighted / (double)bps_gaps : std::nan("");
+    const std::pair<const char *, unsigned long long> rows[] = {
+        {"numContigsExpected", (unsigned long long)n_input}, {"numMappedContigs", (unsigned long long)mapped_contigs},
+        {"numClosedGaps", (unsigned long long)closed}, {"numPartiallyClosedGaps", (unsigned long long)partially},
+        {"numCorrectGaps", (unsigned long long)correct}, {"numBpsExpected", bps_expected}, {"numBpsKnown", bps_known},
+        {"numBpsResult", bps_result}, {"numBpsInGaps", bps_gaps}, {"maximumN50", n50(scaffolds)}, {"inputN50", n50(inputs)},
+        {"resultN50", n50(results)}, {"gapMedian", median(gap_len)}, {"closedGapMedian", median(closed_len)},
+        {"minClosedGap", closed_len.empty() ? none : *std::min_element(closed_len.begin(), closed_len.end())},
+        {"maxClosedGap", closed_len.empty() ? none : *std::max_element(closed_len.begin(), closed_len.end())}};
+    if (json) {
+        printf("{");
+        for (const auto &r : rows) printf("\"%s\":%llu,", r.first, r.second);
+        printf("\"averageInsertionError\":%s}\n", num(avg_err).c_str());
+    } else {
+        for (const auto &r : rows) printf("%-24s%20llu\n", (std::string(r.first) + ":").c_str(), r.second);
+        printf("%-24s%20.3e\n", "averageInsertionError:", avg_err);
+    }
+    dh_gap_report_destroy(rep);
+    dh_db_destroy(T);
+    dh_db_destroy(S);
+    dh_ctx_destroy(ctx);
+    dh_dazz_close(dt), dh_dazz_close(dr), dh_dazz_close(ds);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     g_tool = argv[0];
@@ -2060,8 +2308,9 @@ int main(int argc, char **argv)
     if (g_tool == "mask-repetitive-regions") return tool_mask_repetitive_regions(args);
     if (g_tool == "merge-masks") return tool_merge_masks(args);
     if (g_tool == "filter-mask") return tool_filter_mask(args);
+    if (g_tool == "check-results") return tool_check_results(args);
     die("unknown tool (expected fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv "
         "computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index "
-        "chain-local-alignments propagate-mask validate-regions collect mask-repetitive-regions merge-masks filter-mask)");
+        "chain-local-alignments propagate-mask validate-regions collect mask-repetitive-regions merge-masks filter-mask check-results)");
     return 1;
 }
