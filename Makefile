@@ -11,7 +11,7 @@ TOOLS := tools/daligner tools/damapper tools/datander tools/dazz_tools $(addpref
 
 all: $(LIB) $(SIM) oracle $(TOOLS)
 
-tools/daligner: tools/aligner_main.cpp include/dentist_hip.h $(LIB)
+tools/daligner: tools/aligner_main.cpp tools/cli.h include/dentist_hip.h $(LIB)
 	$(HIPCC) -O2 -std=c++17 -o $@ $< -Ldentist_amd -ldentist_hip -Wl,-rpath,'$$ORIGIN/../dentist_amd'
 
 tools/damapper: tools/daligner
@@ -20,8 +20,10 @@ tools/damapper: tools/daligner
 tools/datander: tools/daligner
 	cp $< $@
 
-tools/dazz_tools: tools/dazz_main.cpp include/dentist_hip.h $(LIB)
-	$(HIPCC) -O2 -std=c++17 -o $@ $< -Ldentist_amd -ldentist_hip -Wl,-rpath,'$$ORIGIN/../dentist_amd'
+# the multi-call binary: main and its table of tools, then the tools by role
+DAZZ_SRCS := $(addprefix tools/,dazz_main.cpp dazz_db.cpp dazz_las.cpp dazz_align.cpp dazz_dentist.cpp dazz_check.cpp)
+tools/dazz_tools: $(DAZZ_SRCS) tools/dazz_tools.h tools/cli.h include/dentist_hip.h $(LIB)
+	$(HIPCC) -O2 -std=c++17 -o $@ $(DAZZ_SRCS) -Ldentist_amd -ldentist_hip -Wl,-rpath,'$$ORIGIN/../dentist_amd'
 
 $(addprefix tools/,$(DAZZ_TOOLS)): tools/dazz_tools
 	cp $< $@

@@ -6,29 +6,13 @@
 // emits is parsed (source/dentist/commandline.d:2886-2955); -m<track> loads the
 // mask files DENTIST writes (dazzler.d:4870-5170) and excludes masked k-mers from seeding.  The mode is chosen
 // by argv[0] (daligner | damapper | datander) or `--mode`.
-#include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
-#include "../include/dentist_hip.h"
-
-static void die(const std::string &msg, int rc = 1)
-{
-    fprintf(stderr, "%s\n", msg.c_str());
-    exit(rc);
-}
-#define CHK(call)                                                                                 \
-    do {                                                                                          \
-        if (int rc_ = (call)) die(std::string(#call) + ": " + dh_last_error(), rc_ < 0 ? -rc_ : rc_); \
-    } while (0)
+#include "cli.h"  // (g_tool stays empty: the messages of this binary carry no prefix but the mode they name themselves)
 
 struct OpenDb {
-    dh_dazz *dz = nullptr;
-    dh_db *dev = nullptr;
+    Dazz dz;
+    Db dev;
     std::string name;  // root[.block] as used in .las file names
 };
 
@@ -48,63 +32,39 @@ static std::string las_name_part(const std::string &arg)
 // way daligner treats a track that was never computed for a block)
 static void apply_masks(const std::string &arg, OpenDb &o, const std::vector<std::string> &tracks)
 {
-    const int32_t n = dh_dazz_nreads(o.dz);
-    std::vector<std::vector<std::pair<int32_t, int32_t>>> per((size_t)n);
+    std::vector<std::vector<std::pair<int32_t, int32_t>>> per((size_t)dh_dazz_nreads(o.dz.get()));
     bool any = false;
     for (const std::string &t : tracks) {
-        std::vector<int64_t> ptr((size_t)n + 1);
-        const int64_t m = dh_dazz_read_mask(o.dz, arg.c_str(), t.c_str(), ptr.data(), nullptr, 0);
-        if (m < 0) {
+        std::vector<int64_t> ptr;
+        std::vector<int32_t> iv;
+        if (!read_mask(o.dz.get(), arg, t, ptr, iv).empty()) {
             fprintf(stderr, "mask track `%s` not found for %s: skipped\n", t.c_str(), arg.c_str());
             continue;
         }
-        std::vector<int32_t> iv((size_t)std::max<int64_t>(2 * m, 2));
-        dh_dazz_read_mask(o.dz, arg.c_str(), t.c_str(), ptr.data(), iv.data(), m);
-        for (int32_t i = 0; i < n; i++)
-            for (int64_t j = ptr[(size_t)i]; j < ptr[(size_t)i + 1]; j++) per[(size_t)i].push_back({iv[(size_t)(2 * j)], iv[(size_t)(2 * j + 1)]});
+        for (size_t i = 0; i < per.size(); i++)
+            for (int64_t j = ptr[i]; j < ptr[i + 1]; j++) per[i].push_back({iv[(size_t)(2 * j)], iv[(size_t)(2 * j + 1)]});
         any = true;
     }
     if (!any) return;
-    std::vector<int64_t> ptr((size_t)n + 1, 0);
+    std::vector<int64_t> ptr;
     std::vector<int32_t> iv;
-    for (int32_t i = 0; i < n; i++) {
-        auto &v = per[(size_t)i];
-        std::sort(v.begin(), v.end());
-        int32_t cb = -1, ce = -1;
-        for (auto &x : v) {
-            if (cb >= 0 && x.first <= ce) {
-                ce = std::max(ce, x.second);
-                continue;
-            }
-            if (cb >= 0) {
-                iv.push_back(cb);
-                iv.push_back(ce);
-            }
-            cb = x.first;
-            ce = x.second;
-        }
-        if (cb >= 0) {
-            iv.push_back(cb);
-            iv.push_back(ce);
-        }
-        ptr[(size_t)i + 1] = (int64_t)iv.size() / 2;
-    }
-    iv.push_back(0);
-    CHK(dh_db_set_mask(o.dev, ptr.data(), iv.data()));
+    merge_intervals(per, ptr, iv);
+    iv.push_back(0);  // (never an empty array)
+    CHK(dh_db_set_mask(o.dev.get(), ptr.data(), iv.data()));
 }
 
 static OpenDb open_db(dh_ctx *ctx, const std::string &arg, const std::vector<std::string> &tracks)
 {
     OpenDb o;
     o.name = las_name_part(arg);
-    CHK(dh_dazz_open(arg.c_str(), &o.dz));
-    CHK(dh_db_create(ctx, dh_dazz_bases(o.dz), dh_dazz_offsets(o.dz), dh_dazz_nreads(o.dz), nullptr, &o.dev));
+    o.dz = open_dazz(arg);
+    CHK(dh_db_create(ctx, dh_dazz_bases(o.dz.get()), dh_dazz_offsets(o.dz.get()), dh_dazz_nreads(o.dz.get()), nullptr, into(o.dev)));
     if (!tracks.empty()) apply_masks(arg, o, tracks);
     return o;
 }
 
 // write one .las: ids are trimmed DB ids (block first id + local index)
-static void write_las(const std::string &path, dh_la_set *set, int afirst, int bfirst, int tspace)
+static void write_las(const std::string &path, const dh_la_set *set, int afirst, int bfirst, int tspace)
 {
     const int64_t n = dh_la_set_count(set);
     // chains that damapper's -n rule discards come back DISABLED: they are not written
@@ -181,8 +141,8 @@ int main(int argc, char **argv)
         if (near_best < 0 || near_best > 1) die(mode + ": -n must be in [0, 1]");
     }
 
-    dh_ctx *ctx = nullptr;
-    CHK(dh_ctx_create(0, nullptr, &ctx));
+    Ctx ctx;
+    CHK(dh_ctx_create(0, nullptr, into(ctx)));
     if (tander) {
         // datander <block> ...: every read of a block against ITSELF, the local alignments off the main diagonal (tandem
         // repeats) -> TAN.<block>.las (DAMASKER; DENTIST's call: `datander -T<n> -s126 -l500 -e0.7 <dam>.<block>`,
@@ -194,23 +154,24 @@ int main(int argc, char **argv)
         o.strands = 1;
         o.skip_self = 3;
         for (const std::string &arg : dbs) {
-            OpenDb A = open_db(ctx, arg, tracks);
-            dh_la_set *set = nullptr;
-            CHK(dh_align_db(ctx, A.dev, A.dev, &o, 0, &set));
-            write_las("TAN." + A.name + ".las", set, dh_dazz_first_id(A.dz), dh_dazz_first_id(A.dz), o.tspace);
-            if (verbose) fprintf(stderr, "datander: %lld local alignments -> TAN.%s.las\n", (long long)dh_la_set_count(set), A.name.c_str());
-            dh_la_set_destroy(set);
-            dh_db_destroy(A.dev);
-            dh_dazz_close(A.dz);
+            const OpenDb A = open_db(ctx.get(), arg, tracks);
+            const int first = dh_dazz_first_id(A.dz.get());
+            LaSet set;
+            CHK(dh_align_db(ctx.get(), A.dev.get(), A.dev.get(), &o, 0, into(set)));
+            write_las("TAN." + A.name + ".las", set.get(), first, first, o.tspace);
+            if (verbose) fprintf(stderr, "datander: %lld local alignments -> TAN.%s.las\n", (long long)dh_la_set_count(set.get()), A.name.c_str());
         }
-        dh_ctx_destroy(ctx);
         return 0;
     }
-    if (mapper) CHK(dh_ctx_set_near_best(ctx, (int32_t)llround(near_best * 1e6)));
-    OpenDb A = open_db(ctx, dbs[0], tracks);
+    if (mapper) CHK(dh_ctx_set_near_best(ctx.get(), (int32_t)llround(near_best * 1e6)));
+    const OpenDb A = open_db(ctx.get(), dbs[0], tracks);
+    const int afirst = dh_dazz_first_id(A.dz.get());
     for (size_t bi = 1; bi < dbs.size(); bi++) {
         const bool same = las_name_part(dbs[bi]) == A.name;
-        OpenDb B = same ? A : open_db(ctx, dbs[bi], tracks);
+        OpenDb other;
+        if (!same) other = open_db(ctx.get(), dbs[bi], tracks);
+        const OpenDb &B = same ? A : other;
+        const int bfirst = dh_dazz_first_id(B.dz.get());
         dh_align_opts oo = o;
         // one DB against itself: every unordered pair once, both records written (daligner's own
         // behaviour); -I also aligns a read against itself, which needs the plain all-vs-all
@@ -219,7 +180,7 @@ int main(int argc, char **argv)
             oo.max_la = std::max(oo.max_la, 64);
             oo.max_cand = std::max(oo.max_cand, 128);
         }
-        dh_la_set *ab = nullptr, *ba = nullptr;
+        LaSet ab, ba;
         // damapper -C, and daligner on two DBs without -A (which writes A.B.las and B.A.las, dazzler.d:6121-6140; the
         // workflow's block pairs `daligner -I ... ref.i ref.j`, Snakefile:998-1022): the second file comes out of the same
         // pass -- the transposed pair of every alignment, through its seed (dh_align_db_transposed; DH-2, the tiled band)
@@ -230,23 +191,12 @@ int main(int argc, char **argv)
         }
         const bool transposed = !same && ((mapper && flagC) || both);
         if (transposed)
-            CHK(dh_align_db_transposed(ctx, A.dev, B.dev, &oo, mapper ? 1 : 0, &ab, &ba));
+            CHK(dh_align_db_transposed(ctx.get(), A.dev.get(), B.dev.get(), &oo, mapper ? 1 : 0, into(ab), into(ba)));
         else
-            CHK(dh_align_db(ctx, A.dev, B.dev, &oo, mapper ? 1 : 0, &ab));
-        write_las(A.name + "." + B.name + ".las", ab, dh_dazz_first_id(A.dz), dh_dazz_first_id(B.dz), o.tspace);
-        if (verbose) fprintf(stderr, "%s: %lld local alignments -> %s.%s.las\n", mode.c_str(), (long long)dh_la_set_count(ab), A.name.c_str(), B.name.c_str());
-        dh_la_set_destroy(ab);
-        if (ba) {
-            write_las(B.name + "." + A.name + ".las", ba, dh_dazz_first_id(B.dz), dh_dazz_first_id(A.dz), o.tspace);
-            dh_la_set_destroy(ba);
-        }
-        if (!same) {
-            dh_db_destroy(B.dev);
-            dh_dazz_close(B.dz);
-        }
+            CHK(dh_align_db(ctx.get(), A.dev.get(), B.dev.get(), &oo, mapper ? 1 : 0, into(ab)));
+        write_las(A.name + "." + B.name + ".las", ab.get(), afirst, bfirst, o.tspace);
+        if (verbose) fprintf(stderr, "%s: %lld local alignments -> %s.%s.las\n", mode.c_str(), (long long)dh_la_set_count(ab.get()), A.name.c_str(), B.name.c_str());
+        if (ba) write_las(B.name + "." + A.name + ".las", ba.get(), bfirst, afirst, o.tspace);
     }
-    dh_db_destroy(A.dev);
-    dh_dazz_close(A.dz);
-    dh_ctx_destroy(ctx);
     return 0;
 }
