@@ -97,6 +97,14 @@ tests/native/libtjoin_host.so: tests/native/tjoin_host.cpp dentist_amd/csrc/dh_t
 tests/native/tjoin_host_san: tests/native/tjoin_host_main.cpp tests/native/tjoin_host.cpp dentist_amd/csrc/dh_tjoin.h
 	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/tjoin_host_main.cpp tests/native/tjoin_host.cpp
 
+# the plan of the seed stage (dentist_amd/csrc/dh_seed_plan.h) behind a C interface: test infrastructure
+tests/native/libseedplan_host.so: tests/native/seedplan_host.cpp dentist_amd/csrc/dh_seed_plan.h
+	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -o $@ $<
+
+# the same harness and a stand-alone main under the host sanitizers (a program of its own: nothing is preloaded)
+tests/native/seedplan_host_san: tests/native/seedplan_host_main.cpp tests/native/seedplan_host.cpp dentist_amd/csrc/dh_seed_plan.h
+	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/seedplan_host_main.cpp tests/native/seedplan_host.cpp
+
 # the lane code and the host plan of the chaining (dentist_amd/csrc/dh_chain.h) compiled for the CPU: test infrastructure
 tests/native/libchain_host.so: tests/native/chain_host.cpp dentist_amd/csrc/dh_chain.h include/dentist_hip.h
 	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -o $@ $<

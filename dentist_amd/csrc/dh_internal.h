@@ -79,11 +79,11 @@ int dh_alloc_bases(hipStream_t st, int64_t total, uint8_t **alloc, uint8_t **bas
 enum DhSlot : int {
     // words shared by an alignment call and the 2-bit packers (several requests, all of DH_STW_COUNT words): DH_STW_* below
     SLOT_STATUS,
-    // dh_align_db* / dh_map_reads (dh_align.cpp: alloc_scratch and the chunk stages): live for one call, rewritten by
+    // dh_align_db* / dh_map_reads (alloc_scratch, dh_align_prepare.cpp, and the chunk stages): live for one call, rewritten by
     // every chunk; the compacted records and trace values of the last chunk stay valid until the next alignment call
     // (dh_la_set.d_trace / d_la / d_item_off point into SLOT_TROUT, SLOT_LAOUT, SLOT_NLA).  Several requests: SLOT_LA and
     // SLOT_TRSLOTS (alloc_scratch, or extend_chunk once a symmetric launch has counted its candidates), SLOT_FSCR (one per
-    // seed tier, sized by the tier), SLOT_UNITS (one per kind of unit)
+    // seed tier, sized by the tier: fscr_scratch, dh_align_seed.cpp), SLOT_UNITS (one per kind of unit)
     SLOT_CAND, SLOT_NCAND, SLOT_NHITS, SLOT_NLA, SLOT_NTR, SLOT_POOL, SLOT_CDJ, SLOT_QUEUE, SLOT_LA, SLOT_TRSLOTS,
     SLOT_COUNTERS, SLOT_SUMS, SLOT_SUMMARY, SLOT_OVF, SLOT_REGS, SLOT_COLD, SLOT_LAOUT, SLOT_TROUT,
     SLOT_FSCR, SLOT_MID_LIST, SLOT_BIG_LIST, SLOT_BIG_HITS,            // seed tiers: slab scratch, the reads of a tier, HBM-staged hits
@@ -91,14 +91,14 @@ enum DhSlot : int {
     // the transposed file of dh_align_db_transposed: same life as the group above
     SLOT_LA2, SLOT_TRSLOTS2, SLOT_NLA2, SLOT_NTR2, SLOT_A_PLANES, SLOT_A_RC_PLANES, SLOT_B_PK2, SLOT_B_RC_PK2, SLOT_LAOUT2,
     SLOT_TROUT2,
-    // the per-chunk copies of B (chunk_copies, dh_align.cpp): made at the start of a chunk, read by its extension
+    // the per-chunk copies of B (chunk_copies, dh_align_prepare.cpp): made at the start of a chunk, read by its extension
     SLOT_CHUNK_RC, SLOT_CHUNK_PK, SLOT_CHUNK_RCPK,
-    // the pile-up join (build_join, dh_align.cpp): built once per call, read by the seeds of every chunk
+    // the pile-up join (build_join, dh_align_join.cpp): built once per call, read by the seeds of every chunk
     SLOT_JOIN_BLOB, SLOT_JOIN_PSUB, SLOT_JOIN_ENTRIES, SLOT_JOIN_SEGTAB, SLOT_JOIN_CURSOR, SLOT_JOIN_HITS,
-    // the mapping join (plan_mj_chunk, dh_align.cpp): planned per chunk, read by that chunk's seeds
+    // the mapping join (plan_mj_chunk, dh_align_seed.cpp): planned per chunk, read by that chunk's seeds
     SLOT_MJ_ENT, SLOT_MJ_SEGOFF, SLOT_MJ_TILE_N, SLOT_MJ_TILE_R, SLOT_MJ_SEG, SLOT_MJ_HSEG, SLOT_MJ_HITS, SLOT_MJ_RHITS,
     SLOT_MJ_SEGTAB, SLOT_MJ_CTR,
-    // the per-group table join (seed_chunk, dh_align.cpp): the units, hit segments and hits of one chunk, read by its seeds
+    // the per-group table join (run_table_join, dh_align_seed.cpp): the units, hit segments and hits of one chunk, read by its seeds
     SLOT_TJ_UNITS, SLOT_TJ_SEGTAB, SLOT_TJ_HITS, SLOT_TJ_CTR,
     // the process rounds (the vote and emit pass of a consensus round, dh_rounds.cpp): live for one round
     SLOT_PR_VOFF, SLOT_PR_VOTES, SLOT_PR_OUT, SLOT_PR_STATUS, SLOT_PR_STAGE, SLOT_PR_SEGS, SLOT_PR_DECISIONS, SLOT_PR_CDIFF,
@@ -190,7 +190,7 @@ enum DhSlot : int {
 enum { DH_STW_STATUS = 0, DH_STW_PACK = 1, DH_STW_PACK_RC = 2, DH_STW_COUNT = 4 };
 static_assert(DH_STW_PACK_RC == DH_STW_PACK + 1, "chunk_copies clears the two flag words with one memset");
 
-// The hit buffer of the pile-up join (build_join, dh_align.cpp) is sized by pile-up depth.  Every template position has
+// The hit buffer of the pile-up join (build_join, dh_align_join.cpp) is sized by pile-up depth.  Every template position has
 // about n p intact copies among the n reads of a pile-up (p: a k-mer survives the errors), every unordered pair of copies
 // is one hit, a group has n L bases: n p^2 / 2 hits per base, i.e. a constant per base PER READ OF DEPTH.  Measured at 13 %
 // error, k = 14: 0.77 hits per base at 60 reads (0.0128 per read of depth), 1.94 at 166 (0.0117) -- the larger one starts a

@@ -215,8 +215,8 @@ def sub_db(db, ids):
 
 
 def chunk_bounds(nreads, chunk_items=1 << 20):
-    """[first read, end read) of every chunk of one mapping call by the rule of align_range (dh_align.cpp): chunks of
-    `chunk_items` items, two items (strands) per read."""
+    """[first read, end read) of every chunk of one mapping call by the rule of align_range (the chunk loop in dh_align.cpp; the
+    chunk size is prepare_dbs', dh_align_prepare.cpp): chunks of `chunk_items` items, two items (strands) per read."""
     per = chunk_items // 2
     return [(r, min(r + per, nreads)) for r in range(0, nreads, per)]
 
