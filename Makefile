@@ -7,7 +7,7 @@ LIB := dentist_amd/libdentist_hip.so
 SIM := dentist_amd/sim/libdh_sim.so
 
 DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index chain-local-alignments propagate-mask validate-regions collect mask-repetitive-regions merge-masks filter-mask check-results
-TOOLS := tools/daligner tools/damapper tools/datander tools/dazz_tools $(addprefix tools/,$(DAZZ_TOOLS))
+TOOLS := tools/daligner tools/damapper tools/datander tools/dazz_tools $(addprefix tools/,$(DAZZ_TOOLS)) tools/output
 
 all: $(LIB) $(SIM) oracle $(TOOLS)
 
@@ -27,6 +27,11 @@ tools/dazz_tools: $(DAZZ_SRCS) tools/dazz_tools.h tools/cli.h include/dentist_hi
 
 $(addprefix tools/,$(DAZZ_TOOLS)): tools/dazz_tools
 	cp $< $@
+
+# `dentist output` is a program of its own over the same helpers (cli.h, dazz_tools.h, the DB paths of dazz_db.cpp): the
+# multi-call binary's table of names is pinned by the recorded command-line replay (tests/golden/tools_cli.json)
+tools/output: tools/dazz_output.cpp tools/dazz_db.cpp tools/dazz_tools.h tools/cli.h include/dentist_hip.h $(LIB)
+	$(HIPCC) -O2 -std=c++17 -o $@ tools/dazz_output.cpp tools/dazz_db.cpp -Ldentist_amd -ldentist_hip -Wl,-rpath,'$$ORIGIN/../dentist_amd'
 
 # one object per translation unit (build/ is git-ignored): `make -j8` rebuilds only what changed
 OBJDIR := build/obj
@@ -181,3 +186,13 @@ tests/native/libcheckgaps_host.so: tests/native/checkgaps_host.cpp dentist_amd/c
 # dust interval of a contig are where this code would overrun
 tests/native/checkgaps_host_san: tests/native/checkgaps_host_main.cpp tests/native/checkgaps_host.cpp dentist_amd/csrc/dh_checkgaps.h include/dentist_hip.h
 	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/checkgaps_host_main.cpp tests/native/checkgaps_host.cpp
+
+# the lane code of the FASTA formatter of dh_output_db (dentist_amd/csrc/dh_outfmt.h) compiled for the CPU: test infrastructure
+tests/native/liboutfmt_host.so: tests/native/outfmt_host.cpp dentist_amd/csrc/dh_outfmt.h
+	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -o $@ $<
+
+# the same harness and a stand-alone main under the host sanitizers (a program of its own: nothing is preloaded); run it once
+# after a change to dh_outfmt.h -- the last segment of a record, the last record's offsets and the bytes behind the end of a
+# chunk are where this code would overrun
+tests/native/outfmt_host_san: tests/native/outfmt_host_main.cpp tests/native/outfmt_host.cpp dentist_amd/csrc/dh_outfmt.h
+	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/outfmt_host_main.cpp tests/native/outfmt_host.cpp

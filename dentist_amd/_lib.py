@@ -140,6 +140,7 @@ SYMBOLS = [
     "dh_mask_set_count", "dh_mask_set_events", "dh_mask_set_sort_passes", "dh_mask_set_groups",
     "dh_check_gaps", "dh_gap_report_destroy", "dh_gap_report_count", "dh_gap_report_summaries", "dh_gap_report_paths",
     "dh_gap_report_aligned", "dh_gap_report_groups",
+    "dh_insertions_from_db", "dh_output_db", "dh_get_output_stats", "dh_output_plan", "dh_out_plan_destroy", "dh_out_plan_array",
 ]
 
 _LIB = None
@@ -841,6 +842,50 @@ class Context:
                                    int(first_contig), int(count), ctypes.byref(h)))
         return GapReport(h)
 
+    def output_db(self, fasta_path, contigs, scaffold_of, headers, gap_len, insertions_db, bed_path=None, agp_path=None,
+                  join_policy="scaffoldGaps", agp_dazzler=False, agp_skip_read_ids=False, read_names=None, line_width=50,
+                  highlight=True, tool=None, input_assembly=None, only="spanning", min_extension_length=100,
+                  max_insertion_error=None, skip_gaps=None):
+        """dh_output_db: `dentist output` with the FASTA text formatted on the device.  contigs: a Db of this context;
+        insertions_db: the path of an insertions.db (read with dh_insertions_from_db against the Db's contig offsets);
+        fasta_path None: stdout.  The other keywords as for output_assembly; max_insertion_error (a fraction, None: no cut)
+        and skip_gaps (pairs of 0-based contig ids) are the filter.  Returns the number of insertions the join policy dropped."""
+        L = lib()
+        vp = ctypes.c_void_p
+        co = np.ascontiguousarray(contigs.off, dtype=np.int64)
+        h = vp()
+        L.dh_insertions_from_db.argtypes = [ctypes.c_char_p, vp, ctypes.c_int32, ctypes.POINTER(vp)]
+        _check(L.dh_insertions_from_db(insertions_db.encode(), co.ctypes.data, len(co) - 1, ctypes.byref(h)))
+        try:
+            o = _output_opts(line_width, highlight, join_policy, agp_dazzler, agp_skip_read_ids, only, min_extension_length, tool, input_assembly)
+            so = np.ascontiguousarray(scaffold_of, dtype=np.int32)
+            gl = np.ascontiguousarray(gap_len, dtype=np.int32) if gap_len is not None else None
+            hs = (ctypes.c_char_p * len(headers))(*[x.encode() for x in headers])
+            rn = (ctypes.c_char_p * len(read_names))(*[x.encode() for x in read_names]) if read_names is not None else None
+            flt = None
+            if max_insertion_error is not None or skip_gaps:
+                sg = np.ascontiguousarray(skip_gaps if skip_gaps else np.zeros((0, 2)), dtype=np.int32).reshape(-1, 2)
+                flt = OutputFilter(int(round(max_insertion_error * 1e6)) if max_insertion_error is not None else 0, len(sg),
+                                   sg.ctypes.data if len(sg) else None)
+            dropped = ctypes.c_int32(0)
+            L.dh_output_db.argtypes = [vp, vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, vp, vp, vp, vp, ctypes.c_int32, vp,
+                                       ctypes.POINTER(OutputOpts), ctypes.POINTER(OutputFilter), ctypes.POINTER(ctypes.c_int32)]
+            _check(L.dh_output_db(self._h, contigs._h, fasta_path.encode() if fasta_path else None, bed_path.encode() if bed_path else None,
+                                  agp_path.encode() if agp_path else None, so.ctypes.data, ctypes.cast(hs, vp),
+                                  gl.ctypes.data if gl is not None else None, h, len(read_names) if read_names is not None else -1,
+                                  ctypes.cast(rn, vp) if rn is not None else None, ctypes.byref(o),
+                                  ctypes.byref(flt) if flt is not None else None, ctypes.byref(dropped)))
+        finally:
+            L.dh_insertions_destroy(h)
+        return int(dropped.value)
+
+    def output_stats(self):
+        """The last output_db of this context in ms: kernels, copies back, fwrite, the whole formatting."""
+        ms = (ctypes.c_double * 4)()
+        lib().dh_get_output_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        _check(lib().dh_get_output_stats(self._h, ms))
+        return dict(kernel=ms[0], copy=ms[1], fwrite=ms[2], total=ms[3])
+
     def tandem_mask(self, las, read_off, first_read=0, min_len=500):
         """dh_la_tandem_mask: TANmask's rule on the device -- the union of [min(abpos, bbpos), max(aepos, bepos)) over the
         records with aread == bread on the same strand that are at least min_len long, per read aread - first_read.  Returns
@@ -1307,6 +1352,7 @@ class Db:
         _check(lib().dh_db_create(ctx._h, bases.ctypes.data, off.ctypes.data, len(off) - 1,
                                   group.ctypes.data if group is not None else None, ctypes.byref(h)))
         self._h = h
+        self.off = off  # (host copy of the offsets: Context.output_db reads an insertions.db against them)
         ctx._dbs.append(weakref.ref(self))
         if mask is not None:
             self.set_mask(mask[0], mask[1])
@@ -2225,7 +2271,65 @@ class OutputOpts(ctypes.Structure):
                 ("min_extension_length", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class OutputFilter(ctypes.Structure):
+    _fields_ = [("max_insertion_error_ppm", ctypes.c_int32), ("nskip", ctypes.c_int32), ("skip_gaps2", ctypes.c_void_p)]
+
+
 JOIN_POLICIES = {"scaffoldGaps": 0, "scaffolds": 1, "contigs": 2}
+
+
+def _output_opts(line_width, highlight, join_policy, agp_dazzler, agp_skip_read_ids, only, min_extension_length, tool, input_assembly):
+    o = OutputOpts()
+    lib().dh_default_output_opts.argtypes = [ctypes.POINTER(OutputOpts)]
+    lib().dh_default_output_opts(ctypes.byref(o))
+    o.line_width, o.highlight, o.join_policy = line_width, int(bool(highlight)), JOIN_POLICIES[join_policy]
+    o.agp_dazzler, o.agp_skip_read_ids = int(bool(agp_dazzler)), int(bool(agp_skip_read_ids))
+    o.only, o.min_extension_length = {"spanning": 1, "extending": 2, "both": 3}[only], int(min_extension_length)
+    if tool is not None:
+        o.tool = tool.encode()
+    if input_assembly is not None:
+        o.input_assembly = input_assembly.encode()
+    return o
+
+
+def output_plan(contig_off, scaffold_of, headers, gap_len, rec, bases_len, join_policy="scaffoldGaps", line_width=50, highlight=True,
+                only="spanning", min_extension_length=100):
+    """dh_output_plan: the plan dh_output_db formats on the device, as a dict of arrays (rec_off, hdr_off, seg_first, seg_base,
+    seg_src, seg_flags, hdr) plus width (host only; the layout is stated in csrc/dh_outfmt.h)."""
+    L = lib()
+    vp = ctypes.c_void_p
+    o = _output_opts(line_width, highlight, join_policy, False, False, only, min_extension_length, None, None)
+    co = np.ascontiguousarray(contig_off, dtype=np.int64)
+    so = np.ascontiguousarray(scaffold_of, dtype=np.int32)
+    gl = np.ascontiguousarray(gap_len, dtype=np.int32) if gap_len is not None else None
+    r = np.ascontiguousarray(rec, dtype=INSERTION_DTYPE)
+    hs = (ctypes.c_char_p * len(headers))(*[x.encode() for x in headers])
+    h = vp()
+    L.dh_output_plan.argtypes = [vp, ctypes.c_int32, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(OutputOpts), ctypes.POINTER(vp)]
+    _check(L.dh_output_plan(co.ctypes.data, len(co) - 1, so.ctypes.data, ctypes.cast(hs, vp), gl.ctypes.data if gl is not None else None,
+                            r.ctypes.data if len(r) else None, len(r), int(bases_len), ctypes.byref(o), ctypes.byref(h)))
+    L.dh_out_plan_array.restype = vp
+    L.dh_out_plan_array.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
+    L.dh_out_plan_destroy.argtypes = [vp]
+    out = {"width": int(line_width)}
+    for which, (name, dt) in enumerate((("rec_off", np.int64), ("hdr_off", np.int64), ("seg_first", np.int64), ("seg_base", np.int64),
+                                        ("seg_src", np.int64), ("seg_flags", np.uint32), ("hdr", np.uint8))):
+        n = ctypes.c_int64(0)
+        ptr = L.dh_out_plan_array(h, which, ctypes.byref(n))
+        out[name] = _arr(ptr, n.value, dt)
+    L.dh_out_plan_destroy(h)
+    return out
+
+
+def insertions_from_db(path, contig_off):
+    """dh_insertions_from_db: an insertions.db (of process_pileups(insertions_db=...), insertiondb_merge or DENTIST) as
+    (rec, bases, (ids, ids_off)) in the dtypes output_assembly takes."""
+    L = lib()
+    co = np.ascontiguousarray(contig_off, dtype=np.int64)
+    h = ctypes.c_void_p()
+    L.dh_insertions_from_db.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]
+    _check(L.dh_insertions_from_db(path.encode(), co.ctypes.data, len(co) - 1, ctypes.byref(h)))
+    return _take_insertions(h, None, True)
 
 
 def output_assembly(fasta_path, contigs, scaffold_of, headers, gap_len, rec, bases, read_ids=None, bed_path=None,

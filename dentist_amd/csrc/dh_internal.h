@@ -231,6 +231,7 @@ struct dh_ctx {
     // produced, never lowered (a capacity hint: results do not depend on it) -- and dh_get_join_counts' four counters
     double join_hit_rate = DH_JOIN_HIT_RATE0;
     int64_t join_launches = 0, join_reruns = 0, join_last_hits = 0, join_first_cap = 0;
+    double out_ms[4] = {0, 0, 0, 0};  // dh_output_db's last call: kernels, copies back, fwrite, the whole call (dh_get_output_stats)
     int32_t near_best_ppm = -1;  // damapper -n of this context (dh_ctx_set_near_best); -1 = the process default
     // second context of the same device (own streams and scratch), created on first use: the process stage runs the
     // two halves of a batch of pile-ups concurrently, one on each (dh_process_pileups)
@@ -394,7 +395,31 @@ struct dh_insertions {
     std::vector<uint16_t> flank_tr;
     std::vector<int32_t> flank_of;   // per record: index of its left overlap in `flank`, -1 if none
     std::vector<int32_t> ids_off, ids;  // per record [ids_off[i], ids_off[i+1]): read ids of the pile-up
+    // dh_insertions_from_db only: per entry of `flank` the A bases its local alignments cover (coveredBases!"contigA",
+    // base.d:640-659) -- `flank` then holds one pseudo record per overlap (first A begin, last A end, diffs summed); empty:
+    // every overlap is one local alignment and covers aepos - abpos
+    std::vector<int64_t> flank_cov;
 };
+
+// dh_output.cpp: the walk of `dentist output` (graph, fixCropping, scaffold starts, linear walks; AGP and BED written on the
+// way) hands the FASTA to a sink, piece by piece in file order.  dh_output_assembly's sink writes through LineWriter; the sink
+// of dh_output_db (dh_outfmt.cpp) records a plan and formats it on the device.
+struct DhOutSink {
+    virtual ~DhOutSink() {}
+    virtual int begin() = 0;                              // open the FASTA: DH_OK, or a failure reported through dh_fail
+    virtual void header(const std::string &line) = 0;     // a record starts: its header line with '>' and '\n'
+    virtual void contig(int32_t c, int64_t from, int64_t upto, bool comp) = 0;  // bases [from, upto) of contig c; comp: reverse-complemented
+    virtual void nrun(int64_t len) = 0;
+    virtual void insertion(int64_t cons_off, int64_t sb, int64_t se, bool comp, bool upper) = 0;  // consensus bases [sb, se) behind cons_off
+    virtual void end_record() = 0;
+    virtual void abandon() = 0;                           // the walk failed: close what begin() opened
+    virtual int finish() = 0;                             // write what is left and close: DH_OK, or a failure reported through dh_fail
+};
+int dh_output_walk(const char *who, DhOutSink &sink, const char *fasta_name, const char *bed_path, const char *agp_path,
+                   const int64_t *contig_off, int32_t ncontigs, const int32_t *scaffold_of, const char *const *headers,
+                   const int32_t *gap_len, const dh_insertion *ins, int32_t nins, const int32_t *read_ids,
+                   const int32_t *read_ids_off, int32_t nreads, const char *const *read_names, const dh_output_opts *opts,
+                   int32_t *dropped);
 
 // Alignment chains as units (base.d:306-421; chain flags dazzler.d:1728-1758, 1991-1998): a record with NEXT (and not
 // START) continues the chain of the record before it (same contig, read and strand).  The view holds one pseudo record

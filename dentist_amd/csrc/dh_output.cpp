@@ -39,6 +39,60 @@ struct LineWriter {
 };
 const char LOWER[5] = {'a', 'c', 'g', 't', 'n'};
 const char UPPER[5] = {'A', 'C', 'G', 'T', 'N'};
+
+// the sink of dh_output_assembly and dh_output_fasta: every base through LineWriter, as before the walk fed a sink
+struct FileSink : DhOutSink {
+    const char *path;
+    const uint8_t *contig_bases, *ins_bases;
+    const int64_t *contig_off;
+    LineWriter w;
+    FileSink(const char *path_, const uint8_t *cb, const int64_t *co, const uint8_t *ib, int32_t width)
+        : path(path_), contig_bases(cb), ins_bases(ib), contig_off(co), w{nullptr, width}
+    {
+    }
+    int begin() override
+    {
+        w.f = fopen(path, "w");
+        return w.f ? DH_OK : dh_fail(DH_EIO, std::string("cannot open ") + path);
+    }
+    void header(const std::string &line) override
+    {
+        if (fwrite(line.data(), 1, line.size(), w.f) != line.size()) w.ok = false;
+    }
+    void contig(int32_t c, int64_t from, int64_t upto, bool comp) override
+    {
+        for (int64_t x = 0; x < upto - from; x++) {
+            uint8_t b = contig_bases[contig_off[c] + (comp ? upto - 1 - x : from + x)];
+            if (comp && b < 4) b = (uint8_t)(3 - b);
+            w.put(LOWER[b < 4 ? b : 4]);
+        }
+    }
+    void nrun(int64_t len) override
+    {
+        for (int64_t x = 0; x < len; x++) w.put('n');
+    }
+    void insertion(int64_t cons_off, int64_t sb, int64_t se, bool comp, bool upper) override
+    {
+        const uint8_t *cons = ins_bases + cons_off;
+        for (int64_t x = 0; x < se - sb; x++) {
+            uint8_t b = comp ? cons[se - 1 - x] : cons[sb + x];
+            if (comp && b < 4) b = (uint8_t)(3 - b);
+            w.put((upper ? UPPER : LOWER)[b < 4 ? b : 4]);
+        }
+    }
+    void end_record() override { w.end_record(); }
+    void abandon() override
+    {
+        if (w.f) fclose(w.f);
+        w.f = nullptr;
+    }
+    int finish() override
+    {
+        const bool closed = fclose(w.f) == 0;
+        w.f = nullptr;
+        return w.ok && closed ? DH_OK : dh_fail(DH_EIO, std::string("short write to ") + path);
+    }
+};
 }  // namespace
 
 // ---- the assembly graph (common/scaffold.d): nodes = (contig, part) with part pre < begin < end < post, numbered
@@ -359,32 +413,46 @@ extern "C" int dh_output_assembly(const char *fasta_path, const char *bed_path, 
     if (!fasta_path || !contig_bases || !contig_off || !scaffold_of || !headers || !opts ||
         (nins > 0 && (!ins || !ins_bases)) || ncontigs < 0 || (read_ids && !read_ids_off))
         return dh_fail(DH_EINVAL, "dh_output_assembly: NULL argument");
+    FileSink sink(fasta_path, contig_bases, contig_off, ins_bases, opts->line_width);
+    return dh_output_walk("dh_output_assembly", sink, fasta_path, bed_path, agp_path, contig_off, ncontigs, scaffold_of, headers,
+                          gap_len, ins, nins, read_ids, read_ids_off, nreads, read_names, opts, dropped);
+}
+
+// the walk behind dh_output_assembly and dh_output_db (`who` names the entry point in messages; fasta_name: the FASTA in the
+// message of a short write)
+int dh_output_walk(const char *who_, DhOutSink &sink, const char *fasta_name, const char *bed_path, const char *agp_path,
+                   const int64_t *contig_off, int32_t ncontigs, const int32_t *scaffold_of, const char *const *headers,
+                   const int32_t *gap_len, const dh_insertion *ins, int32_t nins, const int32_t *read_ids,
+                   const int32_t *read_ids_off, int32_t nreads, const char *const *read_names, const dh_output_opts *opts,
+                   int32_t *dropped)
+{
+    const std::string who(who_);
     const dh_output_opts &o = *opts;
-    if (o.join_policy < 0 || o.join_policy > 2) return dh_fail(DH_EINVAL, "dh_output_assembly: join_policy must be 0, 1 or 2");
-    if (o.only < 0 || o.only > 3) return dh_fail(DH_EINVAL, "dh_output_assembly: only must be 0 (= spanning), 1 spanning, 2 extending or 3 both");
+    if (o.join_policy < 0 || o.join_policy > 2) return dh_fail(DH_EINVAL, who + ": join_policy must be 0, 1 or 2");
+    if (o.only < 0 || o.only > 3) return dh_fail(DH_EINVAL, who + ": only must be 0 (= spanning), 1 spanning, 2 extending or 3 both");
     const int32_t only = o.only == 0 ? 1 : o.only;
     if (agp_path && !o.agp_dazzler && !o.agp_skip_read_ids && !read_names)
-        return dh_fail(DH_EINVAL, "dh_output_assembly: the AGP needs read names, agp_dazzler or agp_skip_read_ids");
+        return dh_fail(DH_EINVAL, who + ": the AGP needs read names, agp_dazzler or agp_skip_read_ids");
     // read ids index read_names[]: offsets monotone, ids inside [0, nreads), names present (nreads < 0: ids unchecked,
     // legal only when no name table is consulted)
     const bool names_used = agp_path && !o.agp_dazzler && !o.agp_skip_read_ids;
-    if (names_used && nreads < 0) return dh_fail(DH_EINVAL, "dh_output_assembly: read names need nreads");
+    if (names_used && nreads < 0) return dh_fail(DH_EINVAL, who + ": read names need nreads");
     if (read_ids) {
-        if (read_ids_off[0] < 0) return dh_fail(DH_EINVAL, "dh_output_assembly: negative read id offset");
+        if (read_ids_off[0] < 0) return dh_fail(DH_EINVAL, who + ": negative read id offset");
         for (int32_t i = 0; i < nins; i++)
             if (read_ids_off[i + 1] < read_ids_off[i])
-                return dh_fail(DH_EINVAL, "dh_output_assembly: read id offsets are not monotone");
+                return dh_fail(DH_EINVAL, who + ": read id offsets are not monotone");
         if (nreads >= 0)
             for (int32_t x = read_ids_off[0]; x < read_ids_off[nins]; x++)
                 if (read_ids[x] < 0 || read_ids[x] >= nreads)
-                    return dh_fail(DH_EINVAL, "dh_output_assembly: read id outside [0, nreads)");
+                    return dh_fail(DH_EINVAL, who + ": read id outside [0, nreads)");
     }
     if (names_used) {
         for (int32_t i = 0; i < nins; i++)
             if (!read_ids && ins[i].status == DH_PILE_OK && (ins[i].ref_read_id < 0 || ins[i].ref_read_id >= nreads))
-                return dh_fail(DH_EINVAL, "dh_output_assembly: reference read id outside [0, nreads)");
+                return dh_fail(DH_EINVAL, who + ": reference read id outside [0, nreads)");
         for (int32_t r = 0; r < nreads; r++)
-            if (!read_names[r]) return dh_fail(DH_EINVAL, "dh_output_assembly: NULL read name");
+            if (!read_names[r]) return dh_fail(DH_EINVAL, who + ": NULL read name");
     }
     // ---- the graph
     AGraph g;
@@ -398,14 +466,14 @@ extern "C" int dh_output_assembly(const char *fasta_path, const char *bed_path, 
         if (ins[i].status != DH_PILE_OK) continue;
         EKey e;
         int32_t seeds[2], nf;
-        if (!insertion_edge(ins[i], ncontigs, e, seeds, nf)) return dh_fail(DH_EINVAL, "dh_output_assembly: insertion outside the contigs");
+        if (!insertion_edge(ins[i], ncontigs, e, seeds, nf)) return dh_fail(DH_EINVAL, who + ": insertion outside the contigs");
         if (ins[i].ins_begin < 0 || ins[i].ins_begin > ins[i].ins_end || ins[i].ins_end > ins[i].cons_len || ins[i].cons_off < 0)
-            return dh_fail(DH_EINVAL, "dh_output_assembly: insertion outside its consensus");
+            return dh_fail(DH_EINVAL, who + ": insertion outside its consensus");
         if (nf == 1) {
             if (!(only & 2) || ins[i].ins_end - ins[i].ins_begin < o.min_extension_length) continue;
         } else if (!(only & 1))
             continue;
-        if (g.edges.count(e)) return dh_fail(DH_EINVAL, nf == 1 ? "dh_output_assembly: two insertions for one extension" : "dh_output_assembly: two insertions for one gap");
+        if (g.edges.count(e)) return dh_fail(DH_EINVAL, who + (nf == 1 ? ": two insertions for one extension" : ": two insertions for one gap"));
         Payload &p = g.edges[e];
         p.kind = K_INS;
         p.ins = i;
@@ -430,24 +498,26 @@ extern "C" int dh_output_assembly(const char *fasta_path, const char *bed_path, 
                 if (p.kind != K_INS) continue;
                 const dh_insertion &r = ins[p.ins];
                 const int32_t f = r.contig_left == c ? 0 : 1;
-                if (cp.nov >= 2) return dh_fail(DH_EINVAL, "dh_output_assembly: too many splice sites on a contig");
+                if (cp.nov >= 2) return dh_fail(DH_EINVAL, who + ": too many splice sites on a contig");
                 cp.ov_seed[cp.nov] = part == BEGIN ? 0 : 1;
                 cp.ov_pos[cp.nov] = f == 0 ? r.left_aepos : r.right_abpos;
                 cp.nov++;
             }
     }
     std::vector<int32_t> starts;
-    if (!scaffold_starts(g, starts)) return dh_fail(DH_EINVAL, "dh_output_assembly: fork in the assembly graph (two insertions on one contig end)");
+    if (!scaffold_starts(g, starts)) return dh_fail(DH_EINVAL, who + ": fork in the assembly graph (two insertions on one contig end)");
     // position of every contig inside its input scaffold (ContigSegment.begin)
     std::vector<int64_t> cbegin((size_t)std::max(ncontigs, 1), 0);
     for (int32_t c = 1; c < ncontigs; c++)
         if (scaffold_of[c] == scaffold_of[c - 1])
             cbegin[(size_t)c] = cbegin[(size_t)c - 1] + (contig_off[c] - contig_off[c - 1]) + (gap_len ? gap_len[c - 1] : 0);
-    FILE *f = fopen(fasta_path, "w");
-    if (!f) return dh_fail(DH_EIO, std::string("cannot open ") + fasta_path);
+    if (int rc = sink.begin()) return rc;
     FILE *bed = nullptr, *agp = nullptr;
-    auto close_all = [&]() {
-        bool ok = fclose(f) == 0;
+    bool sink_open = true;
+    auto close_all = [&]() {  // (the failure paths: the sink gives up what it has)
+        bool ok = true;
+        if (sink_open) sink.abandon();
+        sink_open = false;
         if (bed && fclose(bed) != 0) ok = false;
         if (agp && fclose(agp) != 0) ok = false;
         return ok;
@@ -487,17 +557,16 @@ extern "C" int dh_output_assembly(const char *fasta_path, const char *bed_path, 
         dup[label] = n + 1;
         return u;
     };
-    LineWriter w{f, o.line_width};
     std::vector<EKey> walk;
     std::vector<uint8_t> vis((size_t)4 * (size_t)std::max(ncontigs, 1), 0);
     for (int32_t start : starts) {
         bool cyc = false;
         if (!linear_walk(g, start, nullptr, walk, cyc, vis)) {
             close_all();
-            return dh_fail(DH_EINVAL, "dh_output_assembly: fork in the assembly graph");
+            return dh_fail(DH_EINVAL, who + ": fork in the assembly graph");
         }
         const std::string id = uniq(contig_of(start), header_id(contig_of(start)));
-        ok = ok && fprintf(f, ">%s\tscaffold-%d%s\n", id.c_str(), contig_of(start) + 1, cyc ? "\tisCyclic" : "") > 0;
+        sink.header(">" + id + "\tscaffold-" + std::to_string(contig_of(start) + 1) + (cyc ? "\tisCyclic" : "") + "\n");
         int64_t coord = 1;  // 1-based scaffold coordinate of the next base (output.d currentScaffoldCoord)
         int32_t part = 1;   // currentScaffoldPartId
         bool comp = part_of(start) == END;  // globalComplement
@@ -516,13 +585,9 @@ extern "C" int dh_output_assembly(const char *fasta_path, const char *bed_path, 
                 }
                 if (from > upto || upto > p.len || from < 0) {
                     close_all();
-                    return dh_fail(DH_EINVAL, "dh_output_assembly: splice sites cross on a contig");
+                    return dh_fail(DH_EINVAL, who + ": splice sites cross on a contig");
                 }
-                for (int64_t x = 0; x < upto - from; x++) {
-                    uint8_t b = contig_bases[contig_off[c] + (comp ? upto - 1 - x : from + x)];
-                    if (comp && b < 4) b = (uint8_t)(3 - b);
-                    w.put(LOWER[b < 4 ? b : 4]);
-                }
+                sink.contig(c, from, upto, comp);
                 if (agp) {  // writeAGPContig + writeAGPComponent, output.d:464-531
                     const std::string cid = o.agp_dazzler ? std::to_string(c + 1) : header_id(c);
                     ok = ok && fprintf(agp, "%s\t%lld\t%lld\t%d\tW\t%s\t%lld\t%lld\t%s\tna\n", id.c_str(), (long long)coord,
@@ -531,14 +596,13 @@ extern "C" int dh_output_assembly(const char *fasta_path, const char *bed_path, 
                 }
                 coord += upto - from;
             } else if (p.kind == K_NGAP) {
-                for (int64_t x = 0; x < p.len; x++) w.put('n');
+                sink.nrun(p.len);
                 if (agp)  // writeAGPGap, output.d:533-555
                     ok = ok && fprintf(agp, "%s\t%lld\t%lld\t%d\tN\t%lld\tscaffold\tyes\tna\tunspecified\n", id.c_str(),
                                        (long long)coord, (long long)(coord + p.len - 1), part, (long long)p.len) > 0;
                 coord += p.len;
             } else if (p.kind == K_INS) {
                 const dh_insertion &in = ins[p.ins];
-                const uint8_t *cons = ins_bases + in.cons_off;
                 // the slice on the stored consensus (getInfoForNewSequenceInsertion, insertions.d:230-284) ...
                 const int64_t sb = in.comp ? in.cons_len - in.ins_end : in.ins_begin;
                 const int64_t se = in.comp ? in.cons_len - in.ins_begin : in.ins_end;
@@ -548,11 +612,7 @@ extern "C" int dh_output_assembly(const char *fasta_path, const char *bed_path, 
                 bool first_comp = in.comp != 0;
                 if (!(in.join & DH_JOIN_EXTENSION) && contig_of(at) != in.contig_left && e_anti(e)) first_comp = !first_comp;
                 const bool eff = first_comp != comp;
-                for (int64_t x = 0; x < n; x++) {
-                    uint8_t b = eff ? cons[se - 1 - x] : cons[sb + x];
-                    if (eff && b < 4) b = (uint8_t)(3 - b);
-                    w.put((o.highlight ? UPPER : LOWER)[b < 4 ? b : 4]);
-                }
+                sink.insertion(in.cons_off, sb, se, eff, o.highlight != 0);
                 // the read ids of the pile-up, 1-based, ascending (makeInsertion, processPileUps/package.d:789-798)
                 std::vector<int32_t> ids;
                 if (read_ids)
@@ -584,11 +644,13 @@ extern "C" int dh_output_assembly(const char *fasta_path, const char *bed_path, 
             part++;
             at = to;
         }
-        w.end_record();
+        sink.end_record();
     }
-    ok = ok && w.ok;
+    sink_open = false;
+    const int rc = sink.finish();
     if (!close_all()) ok = false;
-    return ok ? DH_OK : dh_fail(DH_EIO, std::string("short write to ") + fasta_path);
+    if (rc != DH_OK) return rc;
+    return ok ? DH_OK : dh_fail(DH_EIO, std::string("short write to ") + fasta_name);
 }
 
 extern "C" void dh_default_output_opts(dh_output_opts *o)

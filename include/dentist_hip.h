@@ -1320,6 +1320,37 @@ int dh_output_assembly(const char *fasta_path, const char *bed_path, const char 
                        const dh_insertion *ins, int32_t nins, const uint8_t *ins_bases, const int32_t *read_ids,
                        const int32_t *read_ids_off, int32_t nreads, const char *const *read_names,
                        const dh_output_opts *opts, int32_t *dropped);
+/* dh_output_assembly with the FASTA text formatted on the device (dh_outfmt.h, dh_outfmt.hip: every byte of the file is a
+ * function of its position; one lane formats 16 consecutive bytes) for contigs that are a dh_db and insertions that are a
+ * dh_insertions (of dh_process_pileups or dh_insertions_from_db).  Replaces the host writer's fputc per base
+ * (dh_output.cpp LineWriter); AGP and BED stay on the host.  All three files are byte-identical to dh_output_assembly's.
+ * fasta_path NULL: stdout.  The other arguments as for dh_output_assembly.  filter (NULL: none) acts on the insertions before
+ * the graph is built: an insertion with an overlap whose diffs / covered A bases exceeds max_insertion_error_ppm
+ * (ensureHighQualityConsensus, output.d:388-410; averageErrorRate, base.d:695-698) and a gap insertion whose contig pair is
+ * listed (removeBlacklisted, scaffold.d:735-768) are left out; they are not counted in *dropped.  The file goes through
+ * chunks of DH_OUT_CHUNK_MB (a decimal number of MiB, default 256; a multiple of 16 bytes, at least 64): two device and two
+ * page-locked host buffers of that size; the result does not depend on it.  No CPU route: ctx NULL is DH_EINVAL. */
+typedef struct {
+    int32_t max_insertion_error_ppm;  /* --max-insertion-error, commandline.d:1989-1999 (100 000); <= 0: no cut */
+    int32_t nskip;                    /* --skip-gaps / --skip-gaps-file: pairs of 0-based contig ids, first < second */
+    const int32_t *skip_gaps2;
+} dh_output_filter;
+int dh_output_db(dh_ctx *ctx, dh_db *contigs, const char *fasta_path, const char *bed_path, const char *agp_path,
+                 const int32_t *scaffold_of, const char *const *headers, const int32_t *gap_len,
+                 const dh_insertions *ins, int32_t nreads, const char *const *read_names,
+                 const dh_output_opts *opts, const dh_output_filter *filter /* NULL: none */, int32_t *dropped);
+/* Test surface of dh_output_db's plan (host only, nothing written): the walk of dh_output_assembly on the same arrays leaves
+ * one plan per call -- per FASTA record its header bytes, its byte offset in the file and its body as segments (dh_outfmt.h
+ * states the layout).  dh_out_plan_array: which = 0 rec_off, 1 hdr_off, 2 seg_first, 3 seg_base, 4 seg_src (int64), 5 seg_flags
+ * (uint32), 6 header bytes; *n = entries.  ins_bases_len bounds the consensus slices. */
+typedef struct dh_out_plan dh_out_plan;
+int dh_output_plan(const int64_t *contig_off, int32_t ncontigs, const int32_t *scaffold_of, const char *const *headers,
+                   const int32_t *gap_len, const dh_insertion *ins, int32_t nins, int64_t ins_bases_len,
+                   const dh_output_opts *opts, dh_out_plan **out);
+void dh_out_plan_destroy(dh_out_plan *p);
+const void *dh_out_plan_array(const dh_out_plan *p, int32_t which, int64_t *n);
+/* the last dh_output_db of the context, ms: kernels, copies back, fwrite, the whole formatting (plan upload to last write) */
+int dh_get_output_stats(dh_ctx *ctx, double *ms4);
 
 /* ---- DAZZ_DB files on disk (.db / .dam stub + hidden .idx / .bps / .hdr), host only.
  *      Replaces what DENTIST obtains by spawning fasta2DB / fasta2DAM / DBsplit
@@ -1401,6 +1432,16 @@ int dh_pileups_write_db(const dh_pileups *p, const dh_la *las, int64_t n, const 
  * with trace points (tspace = dh_process_opts.tspace_pile) and the sorted 1-based read ids */
 int dh_insertions_write_db(const dh_insertions *r, const int64_t *contig_off, int32_t ncontigs, int32_t tspace,
                            const char *path);
+/* insertions.db back into the records the writers below take (`dentist output` reads the file the same way, output.d:309-319;
+ * inverse of dh_insertions_write_db, dh_insertions.cpp:41-59): for a file of dh_insertions_write_db, of tools/merge-insertions
+ * or of the D binary.  contig_left / contig_right / join from the insertion's nodes (makeJoin, base.d:2680-2722); left_aepos /
+ * right_abpos = getCroppingPosition!"contigA" (common/insertions.d:110-119: front seed: the FIRST local alignment's A begin, back
+ * seed: the LAST one's A end -- an overlap may be a chain); ins_begin / ins_end / comp from getCroppingPosition!"contigB" and
+ * getInfoForNewSequenceInsertion (:122-140, :228-284) in the frame the writers expect; left_diffs / right_diffs summed over
+ * the chain; the consensus (codes 0..3), the read ids 0-based with their offsets; status = DH_PILE_OK.  DH_EINVAL with a
+ * message naming the insertion: a contig id outside [1, ncontigs], a contig_a_len that contradicts contig_off, more than two
+ * overlaps, nodes that are neither a gap join nor an extension, a contig_b_len that differs from the sequence length. */
+int dh_insertions_from_db(const char *path, const int64_t *contig_off, int32_t ncontigs, dh_insertions **out);
 void dh_chaindb_destroy(dh_chaindb *d);
 int32_t dh_chaindb_npiles(const dh_chaindb *d);
 const int32_t *dh_chaindb_pile_counts(const dh_chaindb *d);

@@ -36,6 +36,8 @@ int tool_merge_masks(const Args &args);
 int tool_filter_mask(const Args &args);
 // dazz_check.cpp
 int tool_check_results(const Args &args);
+// dazz_output.cpp: `output`, an executable of its own (its main is there)
+int tool_output(const Args &args);
 
 std::string slurp(FILE *f);
 inline char base_char(uint8_t b) { return "acgtn"[std::min<int>(b, 4)]; }
