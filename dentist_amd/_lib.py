@@ -88,7 +88,7 @@ SYMBOLS = [
     "dh_last_error", "dh_abi_version", "dh_ctx_create", "dh_ctx_destroy", "dh_ctx_sync",
     "dh_default_align_opts", "dh_db_create", "dh_db_destroy", "dh_db_drop_cache", "dh_db_nreads",
     "dh_db_total_bases", "dh_la_set_destroy", "dh_la_set_count", "dh_la_set_trace_len",
-    "dh_la_set_records", "dh_la_set_trace", "dh_la_set_tspace", "dh_get_align_stats", "dh_get_cum_stats", "dh_get_mjoin_counts", "dh_get_join_counts", "dh_get_tjoin_counts", "dh_get_seed_tier_counts", "dh_join_hit_capacity",
+    "dh_la_set_records", "dh_la_set_trace", "dh_la_set_tspace", "dh_get_align_stats", "dh_get_cum_stats", "dh_get_mjoin_counts", "dh_get_join_counts", "dh_get_tjoin_counts", "dh_get_seed_tier_counts", "dh_get_seed_band_counts", "dh_join_hit_capacity",
     "dh_ctx_release_scratch",
     "dh_align_db", "dh_seed_candidates",
     "dh_las_write", "dh_las_read", "dh_default_process_opts", "dh_collect_spanning", "dh_pileups_destroy",
@@ -496,6 +496,14 @@ class Context:
         out = (ctypes.c_int64 * 2)()
         lib().dh_get_seed_tier_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
         _check(lib().dh_get_seed_tier_counts(self._h, out, int(reset)))
+        return int(out[0]), int(out[1])
+
+    def seed_band_counts(self, reset=False):
+        """(reads whose band heads went to the table in LDS, reads that kept the slab of global scratch) of the segment-fed
+        8192- and 16384-entry seed tiers on this context's device since the last reset."""
+        out = (ctypes.c_int64 * 2)()
+        lib().dh_get_seed_band_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
+        _check(lib().dh_get_seed_band_counts(self._h, out, int(reset)))
         return int(out[0]), int(out[1])
 
     def cum_stats(self, reset=False):

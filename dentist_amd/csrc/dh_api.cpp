@@ -168,6 +168,20 @@ extern "C" int dh_get_seed_tier_counts(dh_ctx *c, int64_t *out2, int32_t reset)
     return DH_OK;
 }
 
+extern "C" int dhk_seed_band_counts(unsigned long long *out, int reset);
+
+// (the kernels count on the device: the figures are those of the context's device, whichever context launched)
+extern "C" int dh_get_seed_band_counts(dh_ctx *c, int64_t *out2, int32_t reset)
+{
+    if (!c || !out2) return fail(DH_EINVAL, "dh_get_seed_band_counts: NULL");
+    HIPCHK(hipSetDevice(c->device));
+    unsigned long long v[2] = {0, 0};
+    if (dhk_seed_band_counts(v, reset)) return fail(DH_EHIP, "dh_get_seed_band_counts: the counters could not be read");
+    out2[0] = (int64_t)v[0];
+    out2[1] = (int64_t)v[1];
+    return DH_OK;
+}
+
 extern "C" int dh_get_join_counts(dh_ctx *c, int64_t *out4, int32_t reset)
 {
     if (!c || !out4) return fail(DH_EINVAL, "dh_get_join_counts: NULL");

@@ -34,6 +34,17 @@
 // development / tests: 0 = reads with a bucket above SORT_BMAX hits take the bitonic network as before round 6
 // (DH_SEED_NO_REFINE=1; the order is the same either way)
 __device__ int g_seed_sort_refine = 1;
+// development / tests: 1 = the band phase of the segment-fed 8192- and 16384-entry tiers keeps the per-hit sums and the band
+// heads of every read in its slab of global scratch, as before the head table (DH_SEED_SLAB_BANDS=1; same candidates)
+__device__ int g_seed_slab_bands = 0;
+// reads of those two tiers whose band heads went to the table in LDS [0] and to the slab [1] (dh_get_seed_band_counts); a
+// block counts in LDS and adds its counts when it ends
+__device__ unsigned long long g_seed_band_reads[2];
+__device__ __forceinline__ uint32_t *seed_band_lds()
+{
+    __shared__ uint32_t s_band_reads[2];
+    return s_band_reads;
+}
 #define HIT_QBITS 24
 #define HIT_QMASK ((1u << HIT_QBITS) - 1u)
 #define SEED_THREADS 512
@@ -57,7 +68,9 @@ __device__ __forceinline__ int32_t hit_cov(const uint64_t *h, int32_t i, int32_t
 // ncand = -1 and redone by the LCAP == 0 instantiation, whose hit buffer is a slab of HBM
 // (gcap entries per block, items taken from item_list) -- same code, same results.
 #ifdef DH_SEED_PROF
-__device__ unsigned long long g_seed_prof[12];
+// (a row per tier class: the segment- or directory-fed 8192-entry tier [1], the 16384-entry tier [2], every other tier [0])
+__device__ unsigned long long g_seed_prof_all[3][12];
+#define g_seed_prof g_seed_prof_all[LCAP == 8192 ? 1 : (LCAP == 16384 ? 2 : 0)]
 // (a block's clocks add up in LDS and reach g_seed_prof when the persistent block ends: as ten atomics per read on one
 // cache line -- 10^7 per mapping launch at ~10 ns each -- the instrumentation was what the instrumented kernel waited for)
 __device__ __forceinline__ unsigned long long *seed_prof_lds()
@@ -97,6 +110,9 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
     constexpr bool RANK_ALL = LCAP > 0 && NT <= LANES && LCAP <= 8 * NT;
     constexpr bool SLIM = LCAP > 0 && LCAP <= 4096 && NT > LANES && NT < SEED_THREADS;
     constexpr bool FB_LDS = LCAP > 0 && LCAP <= 4096;  // the band phase's prefix sums and heads live in LDS
+    // HTAB (the segment-fed 8192- and 16384-entry tiers, the pile-up all-vs-all's): a table of the band heads in the unused
+    // tail of the read's own hit buffer where it fits, and a lane group for every long range (both below)
+    constexpr bool HTAB = JOIN && NT == SEED_THREADS && (LCAP == 8192 || LCAP == 16384);
     __shared__ uint64_t lhits[LCAP > 0 ? LCAP : 1];
     __shared__ DhCand cands[2 * CC];
     __shared__ int64_t cband[2 * CC];
@@ -798,6 +814,13 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
     // 5 - 21 ms for the 27 such reads of a configs[2] half (one block each).
     // (the 16384-entry variant fed from segments -- uncapped pile-ups: 166 reads, ~10 000 hits per read -- scans as well,
     // with the wide sums of the HBM variant in a slab of 24 576 words per block; the directory-fed one keeps the walks)
+    // HTAB: only band heads are ever looked up, and a head needs its position and the coverage summed before it.  The
+    // number of heads is known after the first pass of the scan; a read of n hits leaves hits[n .. LCAP) unused, so where
+    // nheads + 1 entries (position << HSH | coverage before the head: the layout of the sums; the last entry is (n, total))
+    // fit behind the hits the second pass writes those and nothing per hit: a band's coverage is the difference of two
+    // neighbouring entries, and the head loop's six to eight dependent loads per head are LDS round trips instead of L2's.
+    // 14 + 18 bits hold every read the table has room for at 8192 (positions <= n <= 8191, k <= 28); the 16384-entry tier
+    // takes 32 + 32.  A read whose table does not fit (n + table > LCAP) keeps the slab.
     constexpr bool FASTB = LCAP <= 8192 || (JOIN && LCAP == 16384);
     constexpr bool FB_BIG = LCAP == 0;
     constexpr bool FB_WIDE = LCAP == 0 || LCAP == 16384;
@@ -811,8 +834,12 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
     __shared__ bsum_t s_wsum[NT / LANES];
     __shared__ int32_t s_nbig;
     constexpr int NBIG = NT <= LANES ? 8 : (SLIM ? 16 : ((LCAP > 0 && LCAP <= 4096) ? 128 : 64));  // (the 8192-entry variant has no LDS to spare; what does not fit walks serially)
-    __shared__ int32_t bigc[NBIG][4];  // candidate band pairs with long hit ranges: (first, end, P, slot)
-    __shared__ unsigned long long s_bestkeys[NBIG];
+    __shared__ int32_t bigc[HTAB ? 1 : NBIG][4];  // candidate band pairs with long hit ranges: (first, end, P, slot)
+    __shared__ unsigned long long s_bestkeys[HTAB ? 1 : NBIG];
+    // HTAB: every long range gets lanes.  Its descriptor is parked in the candidate's own record, which is not final before
+    // emit_cand (score = P, aseq = first, apos = end, then bpos = first hit of the best run); biglist names those slots
+    __shared__ uint16_t biglist[HTAB ? 2 * CC : 1];
+    static_assert(2 * CC <= 65536, "a candidate slot fits a biglist entry");
     const int bs = o.band_shift;
     // seed of a band pair [i, e1): first hit of the same-diagonal run (steps <= k) covering most
     // bases; then the candidate record
@@ -868,6 +895,30 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
         bsum_t base = incl - acc;  // ... plus the wavefronts before this one
         for (int wv = 0; wv < tid / LANES; wv++) base += s_wsum[wv];
         bsum_t run = base;
+        // HTAB: the head table behind the hits, where it fits (the whole block decides alike: n and the block's total)
+        constexpr int TPW = (int)(sizeof(uint64_t) / sizeof(bsum_t));  // table entries per entry of the hit buffer
+        bsum_t *htab = (bsum_t *)(hits + n);
+        bool use_tab = false;
+        int32_t nheads_tab = 0;
+        if constexpr (HTAB) {
+            static_assert(HTAB ? sizeof(bsum_t) * 8 - HSH >= (LCAP == 8192 ? 14 : 15) : true, "a position <= LCAP - 1 (and n) fits an entry");
+            bsum_t tot = 0;
+            for (int wv = 0; wv < NT / LANES; wv++) tot += s_wsum[wv];
+            nheads_tab = (int32_t)(tot >> HSH);
+            use_tab = !g_seed_slab_bands && n + (nheads_tab + 1 + TPW - 1) / TPW <= LCAP;
+            if (tid == 0) {
+                seed_band_lds()[use_tab ? 0 : 1]++;
+                if (use_tab) htab[nheads_tab] = ((bsum_t)n << HSH) | (tot & CMASK);
+            }
+        }
+        if (HTAB && use_tab) {
+            for (int32_t i = x0; i < x1; i++) {
+                const bool head = i == 0 || (hitD(hits[i - 1]) >> bs) != (hitD(hits[i]) >> bs);
+                // (run: heads and coverage before hit i)
+                if (head) htab[(int32_t)(run >> HSH)] = ((bsum_t)i << HSH) | (run & CMASK);
+                run += ((bsum_t)(head ? 1u : 0u) << HSH) | (bsum_t)hit_cov(hits, i, k);
+            }
+        } else
         for (int32_t i = x0; i < x1; i++) {
             const bool head = i == 0 || (hitD(hits[i - 1]) >> bs) != (hitD(hits[i]) >> bs);
             bsum_t v;
@@ -882,41 +933,90 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
         }
         __syncthreads();
         SP(2)
-        const int32_t nheads = (int32_t)(bsum[n - 1] >> HSH);
-        auto band_cov = [&](int32_t rnk) {  // coverage of the band with head number rnk
-            const int32_t st_ = bhead[rnk], en_ = rnk + 1 < nheads ? bhead[rnk + 1] : n;
-            return (int32_t)((bsum[en_ - 1] & CMASK) - (st_ ? (bsum[st_ - 1] & CMASK) : (bsum_t)0));
-        };
-        for (int32_t rnk = tid; rnk < nheads; rnk += NT) {
-            const int32_t i = bhead[rnk];
-            const int64_t band = hitD(hits[i]) >> bs;
-            int32_t covm1 = 0, cov1 = 0, cov2 = 0, e1;
-            const int32_t cov0 = band_cov(rnk);
-            if (rnk > 0 && (hitD(hits[bhead[rnk - 1]]) >> bs) == band - 1) covm1 = band_cov(rnk - 1);
-            int32_t nx = rnk + 1;  // head number of the next band present
-            e1 = nx < nheads ? bhead[nx] : n;
-            if (nx < nheads && (hitD(hits[bhead[nx]]) >> bs) == band + 1) {
-                cov1 = band_cov(nx);
-                nx++;
-                e1 = nx < nheads ? bhead[nx] : n;
-            }
-            if (nx < nheads && (hitD(hits[bhead[nx]]) >> bs) == band + 2) cov2 = band_cov(nx);
-            const int32_t P = cov0 + cov1, Pm1 = covm1 + cov0, Pp1 = cov1 + cov2;
-            if (P < o.hmin || P < Pm1 || P <= Pp1) continue;
-            const int32_t slot = atomicAdd(&s_nc, 1);
-            if (slot >= 2 * CC) continue;
-            if (e1 - i > 16) {
-                // long range: the whole block picks the seed below
-                const int32_t bslot = atomicAdd(&s_nbig, 1);
-                if (bslot < NBIG) {
-                    bigc[bslot][0] = i;
-                    bigc[bslot][1] = e1;
-                    bigc[bslot][2] = P;
-                    bigc[bslot][3] = slot;
-                    continue;
+        if constexpr (HTAB) {
+            // the head loop over (position of head r, coverage of band r): from the slab's arrays or from the head table
+            auto head_loop = [&](const int32_t nheads, auto hpos, auto band_cov) {
+                for (int32_t rnk = tid; rnk < nheads; rnk += NT) {
+                    const int32_t i = hpos(rnk);
+                    const int64_t band = hitD(hits[i]) >> bs;
+                    int32_t covm1 = 0, cov1 = 0, cov2 = 0, e1;
+                    const int32_t cov0 = band_cov(rnk);
+                    if (rnk > 0 && (hitD(hits[hpos(rnk - 1)]) >> bs) == band - 1) covm1 = band_cov(rnk - 1);
+                    int32_t nx = rnk + 1;  // head number of the next band present
+                    e1 = nx < nheads ? hpos(nx) : n;
+                    if (nx < nheads && (hitD(hits[hpos(nx)]) >> bs) == band + 1) {
+                        cov1 = band_cov(nx);
+                        nx++;
+                        e1 = nx < nheads ? hpos(nx) : n;
+                    }
+                    if (nx < nheads && (hitD(hits[hpos(nx)]) >> bs) == band + 2) cov2 = band_cov(nx);
+                    const int32_t P = cov0 + cov1, Pm1 = covm1 + cov0, Pp1 = cov1 + cov2;
+                    if (P < o.hmin || P < Pm1 || P <= Pp1) continue;
+                    const int32_t slot = atomicAdd(&s_nc, 1);
+                    if (slot >= 2 * CC) continue;
+                    if (e1 - i > 16) {
+                        // long range: the whole block picks the seed below
+                        const int32_t bslot = atomicAdd(&s_nbig, 1);
+                        // (at most 2 CC slots are handed out, so bslot < 2 CC)
+                        cands[slot].score = P;
+                        cands[slot].aseq = i;
+                        cands[slot].apos = e1;
+                        biglist[bslot] = (uint16_t)slot;
+                        continue;
+                    }
+                    emit_cand(slot, serial_seed(i, e1), P, band);
                 }
+            };
+            if (use_tab) {
+                head_loop(
+                    nheads_tab, [&](int32_t rnk) { return (int32_t)(htab[rnk] >> HSH); },
+                    [&](int32_t rnk) { return (int32_t)((htab[rnk + 1] & CMASK) - (htab[rnk] & CMASK)); });
+            } else {
+                const int32_t nheads = (int32_t)(bsum[n - 1] >> HSH);
+                head_loop(
+                    nheads, [&](int32_t rnk) { return (int32_t)bhead[rnk]; },
+                    [&](int32_t rnk) {  // coverage of the band with head number rnk
+                        const int32_t st_ = bhead[rnk], en_ = rnk + 1 < nheads ? bhead[rnk + 1] : n;
+                        return (int32_t)((bsum[en_ - 1] & CMASK) - (st_ ? (bsum[st_ - 1] & CMASK) : (bsum_t)0));
+                    });
             }
-            emit_cand(slot, serial_seed(i, e1), P, band);
+        } else {
+            const int32_t nheads = (int32_t)(bsum[n - 1] >> HSH);
+            auto band_cov = [&](int32_t rnk) {  // coverage of the band with head number rnk
+                const int32_t st_ = bhead[rnk], en_ = rnk + 1 < nheads ? bhead[rnk + 1] : n;
+                return (int32_t)((bsum[en_ - 1] & CMASK) - (st_ ? (bsum[st_ - 1] & CMASK) : (bsum_t)0));
+            };
+            for (int32_t rnk = tid; rnk < nheads; rnk += NT) {
+                const int32_t i = bhead[rnk];
+                const int64_t band = hitD(hits[i]) >> bs;
+                int32_t covm1 = 0, cov1 = 0, cov2 = 0, e1;
+                const int32_t cov0 = band_cov(rnk);
+                if (rnk > 0 && (hitD(hits[bhead[rnk - 1]]) >> bs) == band - 1) covm1 = band_cov(rnk - 1);
+                int32_t nx = rnk + 1;  // head number of the next band present
+                e1 = nx < nheads ? bhead[nx] : n;
+                if (nx < nheads && (hitD(hits[bhead[nx]]) >> bs) == band + 1) {
+                    cov1 = band_cov(nx);
+                    nx++;
+                    e1 = nx < nheads ? bhead[nx] : n;
+                }
+                if (nx < nheads && (hitD(hits[bhead[nx]]) >> bs) == band + 2) cov2 = band_cov(nx);
+                const int32_t P = cov0 + cov1, Pm1 = covm1 + cov0, Pp1 = cov1 + cov2;
+                if (P < o.hmin || P < Pm1 || P <= Pp1) continue;
+                const int32_t slot = atomicAdd(&s_nc, 1);
+                if (slot >= 2 * CC) continue;
+                if (e1 - i > 16) {
+                    // long range: the whole block picks the seed below
+                    const int32_t bslot = atomicAdd(&s_nbig, 1);
+                    if (bslot < NBIG) {
+                        bigc[bslot][0] = i;
+                        bigc[bslot][1] = e1;
+                        bigc[bslot][2] = P;
+                        bigc[bslot][3] = slot;
+                        continue;
+                    }
+                }
+                emit_cand(slot, serial_seed(i, e1), P, band);
+            }
         }
         __syncthreads();
         SP(8)
@@ -927,11 +1027,13 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
         // (SLIM: a wavefront per candidate -- an unsampled mapping read has two or three candidates whose band pairs hold
         // most of its ~900 hits: at 16 lanes the walk was 56 dependent rounds by one quarter of a wavefront, 9.4 of the
         // 31 us a 512-thread block spent per read, while every other lane waited at the barrier below; 3.7 us this way)
+        // (HTAB: all of them -- a read of a deep pile-up has a long range per partner it plays B for, 80 and more; beyond
+        // 64 slots they walked serially, one lane each, while the block waited at the barrier above)
         constexpr int GW = SLIM ? LANES : 16;
-        const int32_t nbig = min(s_nbig, NBIG);
+        const int32_t nbig = HTAB ? s_nbig : min(s_nbig, NBIG);
         const int gl = tid & (GW - 1);
         for (int32_t bc = tid / GW; bc < nbig; bc += NT / GW) {
-            const int32_t i = bigc[bc][0], e1 = bigc[bc][1];
+            const int32_t i = HTAB ? cands[biglist[bc]].aseq : bigc[bc][0], e1 = HTAB ? cands[biglist[bc]].apos : bigc[bc][1];
             unsigned long long best = 0ull;
             int32_t carry = i;
             for (int32_t base = i; base < e1; base += GW) {
@@ -961,12 +1063,23 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
                 const unsigned long long ot = __shfl_xor(best, off, GW);
                 best = ot > best ? ot : best;
             }
-            if (gl == 0) s_bestkeys[bc] = best;
+            if (gl == 0) {
+                if constexpr (HTAB)
+                    cands[biglist[bc]].bpos = 0x7FFFFFFF - (int32_t)(uint32_t)best;
+                else
+                    s_bestkeys[bc] = best;
+            }
         }
         __syncthreads();
         SP(9)
-        for (int32_t bc = tid; bc < nbig; bc += NT)
-            emit_cand(bigc[bc][3], 0x7FFFFFFF - (int32_t)(uint32_t)s_bestkeys[bc], bigc[bc][2], hitD(hits[bigc[bc][0]]) >> bs);
+        for (int32_t bc = tid; bc < nbig; bc += NT) {
+            if constexpr (HTAB) {
+                const int32_t slot = biglist[bc];
+                const DhCand d = cands[slot];  // the parked descriptor, read before emit_cand overwrites it
+                emit_cand(slot, d.bpos, d.score, hitD(hits[d.aseq]) >> bs);
+            } else
+                emit_cand(bigc[bc][3], 0x7FFFFFFF - (int32_t)(uint32_t)s_bestkeys[bc], bigc[bc][2], hitD(hits[bigc[bc][0]]) >> bs);
+        }
     } else {
         for (int32_t i = tid; i < n; i += NT) {
             const int64_t band = hitD(hits[i]) >> bs;
@@ -1016,36 +1129,87 @@ __device__ void seed_item(const DbView &B, const IndexView &ix, const JoinView &
     auto strand_of = [&](int32_t c) { return (int32_t)((cband[c] >> (BSTR - bs)) & 1); };
     if (tid < 2) s_ncs[tid] = 0;
     __syncthreads();
-    for (int32_t c = tid; c < nc; c += NT) {
-        const int32_t st = strand_of(c);
-        const int32_t sc = cands[c].score;
-        const int64_t bc = cband[c];
-        int32_t rank = 0;
-        // (no branches, loads of four candidates in flight: the loop is a chain of LDS round trips otherwise)
+    if constexpr (HTAB) {
+        // A read of a deep pile-up has a candidate band pair per partner, 80 to 160 of them: one thread per candidate left
+        // most of the block idle behind a chain of nc LDS round trips, twice.  G lanes share a candidate's loop over the
+        // others and add their counts up (sums of integers: the same ranks).
+        int G = 4;
+        while (G < LANES && nc * 2 * G <= NT) G <<= 1;
+        const int gl = tid & (G - 1);
+        for (int32_t c0 = 0; c0 < nc; c0 += NT / G) {  // (every lane of a group takes part in the shuffles)
+            const int32_t c = c0 + tid / G;
+            const bool on = c < nc;
+            const int32_t cc = on ? c : 0;
+            const int32_t st = strand_of(cc);
+            const int32_t sc = cands[cc].score;
+            const int64_t bc = cband[cc];
+            int32_t rank = 0;
 #pragma unroll 4
-        for (int32_t x = 0; x < nc; x++) {
-            const int64_t bx = cband[x];
-            const int32_t sx = cands[x].score;
-            rank += ((int32_t)((bx >> (BSTR - bs)) & 1) == st && (sx > sc || (sx == sc && bx < bc))) ? 1 : 0;
-        }
-        crank[c] = rank;
-        atomicAdd(&s_ncs[st], 1);
-    }
-    __syncthreads();
-    for (int32_t c = tid; c < nc; c += NT) {
-        const int32_t rank = crank[c], st = strand_of(c);
-        if (rank >= o.max_cand) continue;
-        int32_t pos = rank;
-        if (o.skip_self == 2) {
-            pos = 0;
-            const int32_t ac = cands[c].aseq;
-#pragma unroll 4
-            for (int32_t x = 0; x < nc; x++) {
-                const int32_t ax = cands[x].aseq, rx = crank[x];
-                pos += (strand_of(x) == st && rx < o.max_cand && (ax < ac || (ax == ac && rx < rank))) ? 1 : 0;
+            for (int32_t x = gl; x < nc; x += G) {
+                const int64_t bx = cband[x];
+                const int32_t sx = cands[x].score;
+                rank += ((int32_t)((bx >> (BSTR - bs)) & 1) == st && (sx > sc || (sx == sc && bx < bc))) ? 1 : 0;
+            }
+            for (int off = G >> 1; off > 0; off >>= 1) rank += __shfl_xor(rank, off, G);
+            if (on && gl == 0) {
+                crank[c] = rank;
+                atomicAdd(&s_ncs[st], 1);
             }
         }
-        cand_out[(int64_t)(item + st) * o.max_cand + pos] = cands[c];
+        __syncthreads();
+        for (int32_t c0 = 0; c0 < nc; c0 += NT / G) {
+            const int32_t c = c0 + tid / G;
+            const bool on = c < nc;
+            const int32_t cc = on ? c : 0;
+            const int32_t rank = crank[cc], st = strand_of(cc);
+            const bool kept = on && rank < o.max_cand;
+            int32_t pos = 0;
+            if (o.skip_self == 2) {
+                const int32_t ac = cands[cc].aseq;
+                if (kept) {
+#pragma unroll 4
+                    for (int32_t x = gl; x < nc; x += G) {
+                        const int32_t ax = cands[x].aseq, rx = crank[x];
+                        pos += (strand_of(x) == st && rx < o.max_cand && (ax < ac || (ax == ac && rx < rank))) ? 1 : 0;
+                    }
+                }
+                for (int off = G >> 1; off > 0; off >>= 1) pos += __shfl_xor(pos, off, G);
+            } else
+                pos = rank;
+            if (kept && gl == 0) cand_out[(int64_t)(item + st) * o.max_cand + pos] = cands[cc];
+        }
+    } else {
+        for (int32_t c = tid; c < nc; c += NT) {
+            const int32_t st = strand_of(c);
+            const int32_t sc = cands[c].score;
+            const int64_t bc = cband[c];
+            int32_t rank = 0;
+            // (no branches, loads of four candidates in flight: the loop is a chain of LDS round trips otherwise)
+#pragma unroll 4
+            for (int32_t x = 0; x < nc; x++) {
+                const int64_t bx = cband[x];
+                const int32_t sx = cands[x].score;
+                rank += ((int32_t)((bx >> (BSTR - bs)) & 1) == st && (sx > sc || (sx == sc && bx < bc))) ? 1 : 0;
+            }
+            crank[c] = rank;
+            atomicAdd(&s_ncs[st], 1);
+        }
+        __syncthreads();
+        for (int32_t c = tid; c < nc; c += NT) {
+            const int32_t rank = crank[c], st = strand_of(c);
+            if (rank >= o.max_cand) continue;
+            int32_t pos = rank;
+            if (o.skip_self == 2) {
+                pos = 0;
+                const int32_t ac = cands[c].aseq;
+#pragma unroll 4
+                for (int32_t x = 0; x < nc; x++) {
+                    const int32_t ax = cands[x].aseq, rx = crank[x];
+                    pos += (strand_of(x) == st && rx < o.max_cand && (ax < ac || (ax == ac && rx < rank))) ? 1 : 0;
+                }
+            }
+            cand_out[(int64_t)(item + st) * o.max_cand + pos] = cands[c];
+        }
     }
     if (tid < 2) ncand_out[item + tid] = s_ncs[tid] < o.max_cand ? s_ncs[tid] : o.max_cand;
     SP(4)
@@ -1071,6 +1235,9 @@ k_seed(DbView B, IndexView ix, JoinView jv, DhOpts o, int32_t read0,
     if (threadIdx.x == 0)
         for (int i = 0; i < 12; i++) seed_prof_lds()[i] = 0;
 #endif
+    constexpr bool HTAB = JOIN && NT == SEED_THREADS && (LCAP == 8192 || LCAP == 16384);  // (as in seed_item)
+    if constexpr (HTAB)
+        if (threadIdx.x < 2) seed_band_lds()[threadIdx.x] = 0;
     for (;;) {
         __syncthreads();  // the previous read is finished by every thread (shared state is reused)
         if (threadIdx.x == 0) s_work = (int32_t)atomicAdd(queue, (uint32_t)BATCH);
@@ -1082,8 +1249,14 @@ k_seed(DbView B, IndexView ix, JoinView jv, DhOpts o, int32_t read0,
             const int32_t work = work0 + wi;
             if (work >= nreads) break;
             if (wi) __syncthreads();
-            seed_item<LCAP, JOIN, NT, CC>(B, ix, jv, o, read0, work, (int32_t)blockIdx.x, cand_out, ncand_out, nhits_out,
-                                          status, gbuf, gcap, read_list);
+            // (HTAB: inlined by force.  Left to itself the compiler makes seed_item<16384, true> a function of its own and
+            // keeps the four views it takes by reference in 272 bytes of scratch per lane, read back field by field)
+            if constexpr (HTAB) {
+                [[clang::always_inline]] seed_item<LCAP, JOIN, NT, CC>(B, ix, jv, o, read0, work, (int32_t)blockIdx.x, cand_out,
+                                                                       ncand_out, nhits_out, status, gbuf, gcap, read_list);
+            } else
+                seed_item<LCAP, JOIN, NT, CC>(B, ix, jv, o, read0, work, (int32_t)blockIdx.x, cand_out, ncand_out, nhits_out,
+                                              status, gbuf, gcap, read_list);
         }
     }
 #ifdef DH_SEED_PROF
@@ -1091,6 +1264,8 @@ k_seed(DbView B, IndexView ix, JoinView jv, DhOpts o, int32_t read0,
         for (int i = 0; i < 12; i++)
             if (seed_prof_lds()[i]) atomicAdd(&g_seed_prof[i], seed_prof_lds()[i]);
 #endif
+    if constexpr (HTAB)
+        if (threadIdx.x < 2 && seed_band_lds()[threadIdx.x]) atomicAdd(&g_seed_band_reads[threadIdx.x], (unsigned long long)seed_band_lds()[threadIdx.x]);
 }
 #define SEED_INST(C, J)                                                                           \
     template __global__ void k_seed<C, J>(DbView, IndexView, JoinView, DhOpts, int32_t, int32_t,  \
@@ -1156,16 +1331,36 @@ static void launch_seed(const SeedLaunch &a, uint64_t *gbuf, int32_t gcap)
                        a.jv, a.o, a.read0, a.nreads, a.cand, a.ncand, a.nhits, a.status, gbuf, gcap, a.read_list, a.queue);
 }
 
-// development / tests: DH_SEED_NO_REFINE=1 switches the second counting pass of the seed sort off (read per launch)
+// development / tests: DH_SEED_NO_REFINE=1 switches the second counting pass of the seed sort off, DH_SEED_SLAB_BANDS=1 the
+// head table of the segment-fed 8192- and 16384-entry tiers (read per launch)
 static void seed_sort_switch()
 {
-    static int cur = 1;
+    static int cur = 1, cur_slab = 0;
     const int want = getenv("DH_SEED_NO_REFINE") ? 0 : 1;
     if (want != cur) {
         (void)hipDeviceSynchronize();
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_seed_sort_refine), &want, sizeof(int));
         cur = want;
     }
+    const int want_slab = getenv("DH_SEED_SLAB_BANDS") ? 1 : 0;
+    if (want_slab != cur_slab) {
+        (void)hipDeviceSynchronize();
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_seed_slab_bands), &want_slab, sizeof(int));
+        cur_slab = want_slab;
+    }
+}
+
+// reads of the segment-fed 8192- and 16384-entry tiers since the last reset, on the current device: out[0] took the head
+// table in LDS, out[1] the slab (every launch that counted has finished behind the synchronisation)
+extern "C" int dhk_seed_band_counts(unsigned long long *out, int reset)
+{
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_seed_band_reads), 2 * sizeof(unsigned long long)) != hipSuccess) return 1;
+    if (reset) {
+        const unsigned long long z[2] = {0, 0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_seed_band_reads), z, sizeof(z)) != hipSuccess) return 1;
+    }
+    return 0;
 }
 
 // item0 / nitems: even (both strands of the reads [item0 / 2, (item0 + nitems) / 2))
@@ -1235,17 +1430,23 @@ extern "C" void dhk_seed_big_join(hipStream_t st, DbView B, IndexView ix, DhOpts
 }
 
 #ifdef DH_SEED_PROF
+#undef g_seed_prof
 extern "C" void dhk_seed_prof_dump()
 {
-    unsigned long long h[12];
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_seed_prof), sizeof(h));
-    // (a clock runs from the one before it: the sort is buckets + scatter + ranks, the bands are heads + long ranges + emit)
-    const double per = h[7] ? 1.0 / 100.0 / (double)h[7] : 0.0;
-    fprintf(stderr, "[seed prof] reads %llu: fill %.1f sort %.1f (buckets %.1f scatter %.1f ranks %.1f) bcov %.1f bands %.1f (heads %.1f long ranges %.1f emit %.1f) rank %.1f us/read; %llu reads through the network\n",
-            h[7], h[0] * per, (h[5] + h[6] + h[1]) * per, h[5] * per, h[6] * per, h[1] * per, h[2] * per, (h[8] + h[9] + h[3]) * per,
-            h[8] * per, h[9] * per, h[3] * per, h[4] * per, h[10]);
-    unsigned long long z[12] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_seed_prof), z, sizeof(z));
+    unsigned long long all[3][12];
+    (void)hipMemcpyFromSymbol(all, HIP_SYMBOL(g_seed_prof_all), sizeof(all));
+    static const char *const row[3] = {"other tiers", "8192-entry tier", "16384-entry tier"};
+    for (int t = 0; t < 3; t++) {
+        const unsigned long long *h = all[t];
+        if (!h[7]) continue;
+        // (a clock runs from the one before it: the sort is buckets + scatter + ranks, the bands are heads + long ranges + emit)
+        const double per = 1.0 / 100.0 / (double)h[7];
+        fprintf(stderr, "[seed prof] %s, reads %llu: fill %.1f sort %.1f (buckets %.1f scatter %.1f ranks %.1f) bcov %.1f bands %.1f (heads %.1f long ranges %.1f emit %.1f) rank %.1f us/read; %llu reads through the network\n",
+                row[t], h[7], h[0] * per, (h[5] + h[6] + h[1]) * per, h[5] * per, h[6] * per, h[1] * per, h[2] * per, (h[8] + h[9] + h[3]) * per,
+                h[8] * per, h[9] * per, h[3] * per, h[4] * per, h[10]);
+    }
+    unsigned long long z[3][12] = {{0}};
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_seed_prof_all), z, sizeof(z));
 }
 #endif
 

@@ -177,6 +177,12 @@ int dh_get_tjoin_counts(dh_ctx *ctx, int64_t *out4, int32_t reset);
  * dh_process_pileups the counters of its concurrent parts are added to the context's.  Every tier gives the same
  * candidates.  reset clears both. */
 int dh_get_seed_tier_counts(dh_ctx *ctx, int64_t *out2, int32_t reset);
+/* The band phase of the segment-fed 8192- and 16384-entry seed tiers (the pile-up all-vs-all's): out2[0] reads whose band
+ * heads went to a table in the unused tail of their LDS hit buffer, out2[1] reads whose table did not fit and which kept the
+ * per-hit arrays in global scratch (all of them under DH_SEED_SLAB_BANDS=1).  Counted on the context's device since the
+ * last reset, over every context of the process; the call waits for the device.  Both ways give the same candidates.
+ * reset clears both. */
+int dh_get_seed_band_counts(dh_ctx *ctx, int64_t *out2, int32_t reset);
 /* The capacity (hits) that join's first attempt asks for -- host arithmetic only, no device needed.  bases[g] / reads[g]:
  * bases and reads of group g; rate: hits per base per read of depth (<= 0: the initial figure of a fresh context);
  * free_bytes: device memory free at that moment (< 0: not known, no clamp).  See dh_join_hit_capacity in csrc/dh_join.h. */
