@@ -7,7 +7,8 @@ LIB := dentist_amd/libdentist_hip.so
 SIM := dentist_amd/sim/libdh_sim.so
 
 DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index chain-local-alignments propagate-mask validate-regions collect mask-repetitive-regions merge-masks filter-mask check-results
-TOOLS := tools/daligner tools/damapper tools/datander tools/dazz_tools $(addprefix tools/,$(DAZZ_TOOLS)) tools/output
+PROCESS_TOOLS := process process-pile-ups show-pile-ups
+TOOLS := tools/daligner tools/damapper tools/datander tools/dazz_tools $(addprefix tools/,$(DAZZ_TOOLS)) tools/output $(addprefix tools/,$(PROCESS_TOOLS))
 
 all: $(LIB) $(SIM) oracle $(TOOLS)
 
@@ -32,6 +33,15 @@ $(addprefix tools/,$(DAZZ_TOOLS)): tools/dazz_tools
 # multi-call binary's table of names is pinned by the recorded command-line replay (tests/golden/tools_cli.json)
 tools/output: tools/dazz_output.cpp tools/dazz_db.cpp tools/dazz_tools.h tools/cli.h include/dentist_hip.h $(LIB)
 	$(HIPCC) -O2 -std=c++17 -o $@ tools/dazz_output.cpp tools/dazz_db.cpp -Ldentist_amd -ldentist_hip -Wl,-rpath,'$$ORIGIN/../dentist_amd'
+
+# `dentist process` / `process-pile-ups` / `show-pile-ups`: the tools are in dazz_dentist.cpp, their main in dazz_process.cpp --
+# a program of its own for the same reason as tools/output
+PROCESS_SRCS := $(addprefix tools/,dazz_process.cpp dazz_dentist.cpp dazz_db.cpp)
+tools/process: $(PROCESS_SRCS) tools/dazz_tools.h tools/cli.h include/dentist_hip.h $(LIB)
+	$(HIPCC) -O2 -std=c++17 -o $@ $(PROCESS_SRCS) -Ldentist_amd -ldentist_hip -Wl,-rpath,'$$ORIGIN/../dentist_amd'
+
+tools/process-pile-ups tools/show-pile-ups: tools/process
+	cp $< $@
 
 # one object per translation unit (build/ is git-ignored): `make -j8` rebuilds only what changed
 OBJDIR := build/obj
@@ -196,3 +206,13 @@ tests/native/liboutfmt_host.so: tests/native/outfmt_host.cpp dentist_amd/csrc/dh
 # chunk are where this code would overrun
 tests/native/outfmt_host_san: tests/native/outfmt_host_main.cpp tests/native/outfmt_host.cpp dentist_amd/csrc/dh_outfmt.h
 	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/outfmt_host_main.cpp tests/native/outfmt_host.cpp
+
+# the lane code of the sparse packed read loader (dentist_amd/csrc/dh_bpsload.h) compiled for the CPU: test infrastructure
+tests/native/libbpsload_host.so: tests/native/bpsload_host.cpp dentist_amd/csrc/dh_bpsload.h
+	g++ -O2 -g -shared -fPIC -std=c++17 -Wall -o $@ $<
+
+# the same harness and a stand-alone main under the host sanitizers (a program of its own: nothing is preloaded); run it once
+# after a change to dh_bpsload.h -- the fifth packed byte of a window, the last byte of a read's run and the ragged windows at
+# the ends of a chunk are where this code would overrun
+tests/native/bpsload_host_san: tests/native/bpsload_host_main.cpp tests/native/bpsload_host.cpp dentist_amd/csrc/dh_bpsload.h
+	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/bpsload_host_main.cpp tests/native/bpsload_host.cpp

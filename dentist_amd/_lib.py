@@ -141,6 +141,8 @@ SYMBOLS = [
     "dh_check_gaps", "dh_gap_report_destroy", "dh_gap_report_count", "dh_gap_report_summaries", "dh_gap_report_paths",
     "dh_gap_report_aligned", "dh_gap_report_groups",
     "dh_insertions_from_db", "dh_output_db", "dh_get_output_stats", "dh_output_plan", "dh_out_plan_destroy", "dh_out_plan_array",
+    "dh_dazz_load_reads", "dh_get_load_stats", "dh_db_get_bases", "dh_db_get_offsets", "dh_pileups_from_db", "dh_process_pileups_db",
+    "dh_process_pileups_db_batches",
 ]
 
 _LIB = None
@@ -887,6 +889,13 @@ class Context:
             L.dh_insertions_destroy(h)
         return int(dropped.value)
 
+    def process_pileups_db(self, contigs, reads_db_path, pileups_path, opts, first=0, count=-1, repeat_mask=None, insertions_db=None,
+                           read_ids=False):
+        """dh_process_pileups_db: `dentist process --batch` on files -- pile-ups [first, first + count) of pile-ups.db (count -1:
+        to the end), only the reads they name loaded from the reads DB.  Returns what process_pileups returns (records in node
+        order, read ids of the whole DB)."""
+        return _process_pileups_db(self, contigs, reads_db_path, pileups_path, opts, first, count, repeat_mask, insertions_db, read_ids)
+
     def output_stats(self):
         """The last output_db of this context in ms: kernels, copies back, fwrite, the whole formatting."""
         ms = (ctypes.c_double * 4)()
@@ -1364,6 +1373,32 @@ class Db:
         ctx._dbs.append(weakref.ref(self))
         if mask is not None:
             self.set_mask(mask[0], mask[1])
+
+    @classmethod
+    def _from_handle(cls, ctx, h):
+        """A DB the library made (load_reads): the handle is owned by the new object."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self._h = h
+        L = lib()
+        n = L.dh_db_nreads(h)
+        self.off = np.zeros(n + 1, dtype=np.int64)
+        L.dh_db_get_offsets.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        _check(L.dh_db_get_offsets(h, self.off.ctypes.data))
+        ctx._dbs.append(weakref.ref(self))
+        return self
+
+    def bases(self, first=0, count=None):
+        """dh_db_get_bases: the base codes of sequences [first, first + count) from the device, one uint8 array."""
+        n = len(self.off) - 1
+        count = n - first if count is None else count
+        if first < 0 or count < 0 or first + count > n:
+            raise DhError(-1, "Db.bases: sequences outside the DB")
+        out = np.zeros(int(self.off[first + count] - self.off[first]), dtype=np.uint8)
+        L = lib()
+        L.dh_db_get_bases.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64]
+        _check(L.dh_db_get_bases(self._h, first, count, out.ctypes.data if len(out) else None, len(out)))
+        return out
 
     def drop_cache(self):
         _check(lib().dh_db_drop_cache(self._h))
@@ -2514,6 +2549,57 @@ class DazzDb:
 
     def seq(self, i):
         return self.bases[self.off[i]:self.off[i + 1]]
+
+
+def load_reads(ctx, path, ids):
+    """dh_dazz_load_reads: the reads `ids` (ascending, distinct ids of the trimmed view of `path`, which may name a block) from
+    disk to a device Db, without opening the DB on the host.  DH_LOAD_CHUNK_MB sets the packed MiB per chunk."""
+    v = np.ascontiguousarray(ids, dtype=np.int32)
+    h = ctypes.c_void_p()
+    L = lib()
+    L.dh_dazz_load_reads.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]
+    _check(L.dh_dazz_load_reads(ctx._h, path.encode(), v.ctypes.data if len(v) else None, len(v), ctypes.byref(h)))
+    return Db._from_handle(ctx, h)
+
+
+def load_stats(ctx):
+    """dh_get_load_stats: the context's last load_reads -- ms of file reads, uploads, kernels and the whole call; packed bytes
+    read, bases written, runs, chunks."""
+    ms, cnt = (ctypes.c_double * 4)(), (ctypes.c_int64 * 4)()
+    L = lib()
+    L.dh_get_load_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _check(L.dh_get_load_stats(ctx._h, ms, cnt))
+    return {"ms_file": ms[0], "ms_copy": ms[1], "ms_kernel": ms[2], "ms_total": ms[3], "packed_bytes": cnt[0], "bases": cnt[1],
+            "runs": cnt[2], "chunks": cnt[3]}
+
+
+def pileups_from_db(path, first, count, contig_off):
+    """dh_pileups_from_db: pile-ups [first, first + count) of a pile-ups.db (count -1: to the end) as (Pileups ordered by node,
+    las, trace, tspace, file_index) -- file_index[i] = where pile-up i stood in the file."""
+    co = np.ascontiguousarray(contig_off, dtype=np.int64)
+    hp, hs, fi = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    L = lib()
+    L.dh_pileups_from_db.argtypes = [ctypes.c_char_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                     ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]
+    _check(L.dh_pileups_from_db(path.encode(), first, count, co.ctypes.data, len(co) - 1, ctypes.byref(hp), ctypes.byref(hs), ctypes.byref(fi)))
+    piles = Pileups(None, None, None, _handle=hp)
+    L.dh_shard_free.argtypes = [ctypes.c_void_p]
+    file_index = np.frombuffer(ctypes.string_at(fi.value, 4 * len(piles)), dtype=np.int32).copy() if len(piles) else np.zeros(0, np.int32)
+    L.dh_shard_free(fi)
+    las, trace, ts = _take_la_set(hs)
+    return piles, las, trace, ts, file_index
+
+
+def _process_pileups_db(ctx, contigs, reads_db_path, pileups_path, opts, first=0, count=-1, repeat_mask=None, insertions_db=None,
+                        read_ids=False):
+    L = lib()
+    h = ctypes.c_void_p()
+    keep, rp, ri = _mask_args(repeat_mask)
+    L.dh_process_pileups_db.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
+    _check(L.dh_process_pileups_db(ctx._h if ctx is not None else None, contigs._h, reads_db_path.encode(), pileups_path.encode(), first, count,
+                                   rp, ri, ctypes.byref(opts), ctypes.byref(h)))
+    return _take_insertions(h, insertions_db, read_ids)
 
 
 def dazz_write_mask(db_path, name, ptr, iv):

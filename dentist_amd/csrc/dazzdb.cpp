@@ -19,35 +19,11 @@
 #include <vector>
 
 #include "../../include/dentist_hip.h"
+#include "dh_dazzfmt.h"
 
 int dh_fail(int code, const std::string &msg);
 
 namespace {
-
-#define DB_QV 0x03ff
-#define DB_CCS 0x0400
-#define DB_BEST 0x0800
-#define DB_ALL 0x1
-
-#pragma pack(push, 1)
-struct DazzHeader {  // image of struct DAZZ_DB as fwrite()n by fasta2DB/fasta2DAM, 112 bytes
-    int32_t ureads, treads, cutoff, allarr;
-    float freq[4];
-    int32_t maxlen, pad0;
-    int64_t totlen;
-    int32_t nreads, trimmed, part, ufirst, tfirst, pad1;
-    int64_t path;
-    int32_t loaded, pad2;
-    int64_t bases, reads, tracks;
-};
-struct DazzRead {  // struct DAZZ_READ, 40 bytes
-    int32_t origin, rlen, fpulse, pad0;
-    int64_t boff, coff;
-    int32_t flags, pad1;
-};
-#pragma pack(pop)
-static_assert(sizeof(DazzHeader) == 112, "DAZZ_DB image");
-static_assert(sizeof(DazzRead) == 40, "DAZZ_READ image");
 
 struct Paths {
     std::string stub, dir, root, ext;
@@ -340,12 +316,11 @@ struct dh_dazz {
     std::string root;
 };
 
-// Open a DB or one block of it ("name.3"): the TRIMMED view the aligners work on -- reads shorter
-// than the cutoff (and, for .db without -a, non-best reads) are invisible and ids are trimmed ids.
-extern "C" int dh_dazz_open(const char *path, dh_dazz **out)
+// The stub and the .idx of a DB or of one block of it ("name.3").
+int dh_dazz_view_open(const char *path, DazzView &v)
 {
     Paths p;
-    if (!path || !out || !split_path(std::string(path), p, true)) return dh_fail(DH_EIO, std::string("DAZZ_DB not found: ") + (path ? path : ""));
+    if (!path || !split_path(std::string(path), p, true)) return dh_fail(DH_EIO, std::string("DAZZ_DB not found: ") + (path ? path : ""));
     FILE *st = fopen(p.stub.c_str(), "r");
     if (!st) return dh_fail(DH_EIO, "cannot open " + p.stub);
     int nfiles = 0, nblocks = 0, cutoff = 0, all = 0;
@@ -356,12 +331,11 @@ extern "C" int dh_dazz_open(const char *path, dh_dazz **out)
         fclose(st);
         return dh_fail(DH_EIO, "bad stub " + p.stub);
     }
-    std::vector<std::pair<int, std::string>> prologs;  // (cumulative read count, prolog) per input file
     for (int i = 0; i < nfiles; i++) {
         if (!fgets(line, sizeof(line), st)) break;
         int cum = 0;
         char fname[2048], prolog[2048];
-        if (sscanf(line, " %d %2047s %2047s", &cum, fname, prolog) == 3) prologs.push_back({cum, std::string(prolog)});
+        if (sscanf(line, " %d %2047s %2047s", &cum, fname, prolog) == 3) v.prologs.push_back({cum, std::string(prolog)});
     }
     if (fgets(line, sizeof(line), st)) sscanf(line, "blocks = %d", &nblocks);
     if (nblocks > 0 && fgets(line, sizeof(line), st)) {
@@ -375,29 +349,45 @@ extern "C" int dh_dazz_open(const char *path, dh_dazz **out)
     if (p.block > 0 && (p.block > nblocks || (int)blocks.size() != nblocks + 1))
         return dh_fail(DH_EIO, "block " + std::to_string(p.block) + " does not exist in " + p.stub);
     FILE *idx = fopen(p.hidden("idx").c_str(), "rb");
-    FILE *bps = fopen(p.hidden("bps").c_str(), "rb");
-    if (!idx || !bps) {
-        if (idx) fclose(idx);
-        if (bps) fclose(bps);
-        return dh_fail(DH_EIO, "cannot open hidden files of " + p.stub);
-    }
-    DazzHeader h;
-    if (fread(&h, sizeof(h), 1, idx) != 1) {
+    if (!idx) return dh_fail(DH_EIO, "cannot open hidden files of " + p.stub);
+    if (fread(&v.h, sizeof(v.h), 1, idx) != 1 || v.h.ureads < 0) {
         fclose(idx);
-        fclose(bps);
         return dh_fail(DH_EIO, "short .idx");
     }
-    std::vector<DazzRead> reads((size_t)h.ureads);
-    if (h.ureads && fread(reads.data(), sizeof(DazzRead), reads.size(), idx) != reads.size()) {
+    v.reads.resize((size_t)v.h.ureads);
+    if (v.h.ureads && fread(v.reads.data(), sizeof(DazzRead), v.reads.size(), idx) != v.reads.size()) {
         fclose(idx);
-        fclose(bps);
         return dh_fail(DH_EIO, "short .idx");
     }
     fclose(idx);
-    const bool is_dam = p.ext == ".dam";
+    v.stub = p.stub;
+    v.root = p.root;
+    v.bps_path = p.hidden("bps");
+    v.hdr_path = p.hidden("hdr");
+    v.is_dam = p.ext == ".dam";
+    v.ulo = p.block > 0 ? blocks[(size_t)p.block - 1].first : 0;
+    v.uhi = p.block > 0 ? blocks[(size_t)p.block].first : v.h.ureads;
+    v.tfirst = p.block > 0 ? blocks[(size_t)p.block - 1].second : 0;
+    if (v.ulo < 0 || v.uhi > v.h.ureads || v.ulo > v.uhi) return dh_fail(DH_EIO, "bad block table in " + p.stub);
+    return DH_OK;
+}
+
+// Open a DB or one block of it ("name.3"): the TRIMMED view the aligners work on -- reads shorter
+// than the cutoff (and, for .db without -a, non-best reads) are invisible and ids are trimmed ids.
+extern "C" int dh_dazz_open(const char *path, dh_dazz **out)
+{
+    if (!out) return dh_fail(DH_EIO, std::string("DAZZ_DB not found: ") + (path ? path : ""));
+    DazzView v;
+    if (int rc = dh_dazz_view_open(path, v)) return rc;
+    FILE *bps = fopen(v.bps_path.c_str(), "rb");
+    if (!bps) return dh_fail(DH_EIO, "cannot open hidden files of " + v.stub);
+    const DazzHeader &h = v.h;
+    const std::vector<DazzRead> &reads = v.reads;
+    const std::vector<std::pair<int, std::string>> &prologs = v.prologs;
+    const bool is_dam = v.is_dam;
     std::string hdrs;
     if (is_dam) {
-        FILE *hf = fopen(p.hidden("hdr").c_str(), "rb");
+        FILE *hf = fopen(v.hdr_path.c_str(), "rb");
         if (hf) {
             char buf[65536];
             size_t got;
@@ -410,16 +400,14 @@ extern "C" int dh_dazz_open(const char *path, dh_dazz **out)
     db->ureads = h.ureads;
     db->treads = h.treads;
     db->cutoff = h.cutoff;
-    db->root = p.root;
-    const int ulo = p.block > 0 ? blocks[(size_t)p.block - 1].first : 0;
-    const int uhi = p.block > 0 ? blocks[(size_t)p.block].first : h.ureads;
-    db->tfirst = p.block > 0 ? blocks[(size_t)p.block - 1].second : 0;
+    db->root = v.root;
+    const int ulo = v.ulo, uhi = v.uhi;
+    db->tfirst = v.tfirst;
     db->off.push_back(0);
     std::vector<uint8_t> packed;
     for (int i = ulo; i < uhi; i++) {
         const DazzRead &r = reads[(size_t)i];
-        const bool keep = r.rlen >= h.cutoff && (is_dam || (h.allarr & DB_ALL) || (r.flags & DB_BEST));
-        if (!keep) continue;
+        if (!v.keep(r)) continue;
         packed.resize(((size_t)r.rlen + 3) / 4);
         if (fseek(bps, (long)r.boff, SEEK_SET) != 0 ||
             (!packed.empty() && fread(packed.data(), 1, packed.size(), bps) != packed.size())) {

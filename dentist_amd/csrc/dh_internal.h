@@ -232,6 +232,10 @@ struct dh_ctx {
     double join_hit_rate = DH_JOIN_HIT_RATE0;
     int64_t join_launches = 0, join_reruns = 0, join_last_hits = 0, join_first_cap = 0;
     double out_ms[4] = {0, 0, 0, 0};  // dh_output_db's last call: kernels, copies back, fwrite, the whole call (dh_get_output_stats)
+    // dh_dazz_load_reads' last call (dh_get_load_stats): ms of file reads, uploads, kernels, the whole call; packed bytes read,
+    // bases written, runs, chunks
+    double load_ms[4] = {0, 0, 0, 0};
+    int64_t load_bytes[4] = {0, 0, 0, 0};
     int32_t near_best_ppm = -1;  // damapper -n of this context (dh_ctx_set_near_best); -1 = the process default
     // second context of the same device (own streams and scratch), created on first use: the process stage runs the
     // two halves of a batch of pile-ups concurrently, one on each (dh_process_pileups)

@@ -1369,6 +1369,25 @@ int dh_dazz_split(const char *path, int32_t cutoff, int32_t all, int64_t size_mb
 /* path may name a block ("reads.3"); the trimmed view is returned (ids are trimmed ids) */
 int dh_dazz_open(const char *path, dh_dazz **out);
 void dh_dazz_close(dh_dazz *db);
+/* ---- sparse packed read loader: selected reads of a DAZZ_DB from disk to the device without the host unpack of dh_dazz_open
+ *      (which reads the whole .bps and unpacks it base by base on one host thread; `dentist process --batch` touches a few
+ *      thousand reads of a DB with a million, processPileUps/package.d:96-159).  Kernel: csrc/dh_bpsload.hip.
+ *   Contract.  ids[n] are ascending, distinct ids of the view dh_dazz_open(db_path) would return (trimmed; a block path is
+ *      allowed).  *out is an ungrouped DB of n sequences in that order, the DB dh_db_create would build from the matching
+ *      slices of dh_dazz_bases.  n < 1, unsorted ids, duplicate ids and ids outside the view are DH_EINVAL.
+ *   How.  Only the stub and the .idx are read whole.  The reads' packed byte ranges [boff, boff + ceil(rlen / 4)) are merged
+ *      into runs where they touch in the file; not a byte of the .bps outside the runs is read.  The runs go chunk by chunk
+ *      (DH_LOAD_CHUNK_MB packed MiB, a decimal number, default 64, at least one read; the result does not depend on it) through
+ *      two page-locked buffers; a chunk is uploaded and unpacked on the context's stream while the next one is read.  The packed
+ *      copies and the index of the DB stay lazy, as for any other DB.
+ *   dh_get_load_stats: the context's last call -- ms4 = file reads, uploads, kernels, the whole call; counts4 = packed bytes
+ *      read, bases written, runs, chunks.
+ *   dh_db_get_bases: the bases (codes) of sequences [first, first + count) of any DB, device -> host; cap = bytes of `out`.
+ *   dh_db_get_offsets: off[dh_db_nreads + 1] of any DB. */
+int dh_dazz_load_reads(dh_ctx *ctx, const char *db_path, const int32_t *ids, int32_t n, dh_db **out);
+int dh_get_load_stats(dh_ctx *ctx, double *ms4, int64_t *counts4);
+int dh_db_get_bases(dh_db *db, int32_t first, int32_t count, uint8_t *out, int64_t cap);
+int dh_db_get_offsets(const dh_db *db, int64_t *off);
 int32_t dh_dazz_nreads(const dh_dazz *db);
 int32_t dh_dazz_first_id(const dh_dazz *db);         /* trimmed id of the first read of the block */
 const uint8_t *dh_dazz_bases(const dh_dazz *db);      /* base codes 0..3, concatenated              */
@@ -1448,6 +1467,44 @@ int dh_insertions_write_db(const dh_insertions *r, const int64_t *contig_off, in
  * message naming the insertion: a contig id outside [1, ncontigs], a contig_a_len that contradicts contig_off, more than two
  * overlaps, nodes that are neither a gap join nor an extension, a contig_b_len that differs from the sequence length. */
 int dh_insertions_from_db(const char *path, const int64_t *contig_off, int32_t ncontigs, dh_insertions **out);
+/* pile-ups.db back into pile-ups (`dentist process` reads the file the same way, processPileUps/package.d:96-118; inverse of
+ * dh_pileups_write_db): for a file of that function, of tools/collect or of the D binary.  Pile-ups [first, first + count) of the
+ * file are taken (count -1: to the end; --batch counts in file order, so the selection comes before any ordering).
+ *   Records.  Every SeededAlignment becomes the consecutive records of one chain in *set: aread / bread the 0-based contig_a_id - 1
+ *      / contig_b_id - 1, DH_FLAG_COMP from the chain's flag, trace values copied, tspace the file's.  The members of a chain
+ *      (nla > 1) follow their first record in file order with the chain flags of a chained .las (first: DH_FLAG_START |
+ *      DH_FLAG_BEST, others: DH_FLAG_NEXT; dazzler.d:1728-1758); a chain of one record carries neither.
+ *   Pile-ups.  The nodes (contig0, seed0, contig1, seed1) of a pile-up come from its entries with two seeded alignments,
+ *      normalised to contig0 < contig1 (the entry's sides are exchanged where needed); a pile-up whose entries all have one is
+ *      an extension pile-up; a one-alignment entry of a gap pile-up is matched to its flank by (contig, seed).  Triples are
+ *      (read id, index of the chain's first record on flank 0 or -1, the same on flank 1).  *piles is ordered by node, as
+ *      dh_pileups_create_joins wants it; (*file_index)[i] (file_index may be NULL; release with dh_shard_free) = where pile-up i
+ *      of *piles stood in the file.
+ *   DH_EINVAL, the message naming the pile-up's index in the file: entries that disagree about the nodes, a contig joined with
+ *      itself, a contig id outside [1, ncontigs], a contig_a_len that contradicts contig_off, a trace that does not sum to the
+ *      record's A and B extents (points on the multiples of tspace inside [a_begin, a_end), B parts summing to b_end - b_begin);
+ *      also first or count outside the file.  Host only. */
+int dh_pileups_from_db(const char *path, int32_t first, int32_t count, const int64_t *contig_off, int32_t ncontigs,
+                       dh_pileups **piles, dh_la_set **set, int32_t **file_index);
+/* `dentist process --batch` on files (processPileUps/package.d:96-159): dh_pileups_from_db, the sorted distinct read ids of the
+ * triples through dh_dazz_load_reads (the reads DB is never opened whole), every contig_b_len checked against the loaded read
+ * (DH_EINVAL), read ids renumbered to positions in the sparse DB (a monotone map: every tie broken by read id falls as before),
+ * dh_process_pileups_masked with tspace_map = the file's tspace, ref_read_id and dh_insertions_read_ids translated back to ids
+ * of the whole DB.  The result is bit-identical to dh_process_pileups_masked on the whole reads DB with the same pile-ups
+ * (records in node order).  An empty selection returns an empty result and does not touch the device (ctx may be NULL then).
+ * dh_process_pileups_db_batches: the batches of the command (pileUpBatches, commandline.d:1174-1281) as ONE such call -- the
+ * pile-ups [ranges2[2 k], ranges2[2 k + 1]) of the file for every k in the order given (an end of -1: the end of the file;
+ * ranges that intersect are DH_EINVAL).  only: 0 both, 1 spanning (gap pile-ups), 2 extending (extension pile-ups), applied to
+ * the loaded pile-ups first.  sorted != 0: the records in the order of Insertion.opCmp (processPileUps/package.d:156) instead
+ * of node order.  *file_index = per record its pile-up's index in the file, *skipped[*nskipped] = the file indices `only` kept
+ * out (each may be NULL; release with dh_shard_free). */
+int dh_process_pileups_db(dh_ctx *ctx, dh_db *contigs, const char *reads_db_path, const char *pileups_path, int32_t first,
+                          int32_t count, const int64_t *rep_ptr, const int32_t *rep_iv, const dh_process_opts *opts,
+                          dh_insertions **out);
+int dh_process_pileups_db_batches(dh_ctx *ctx, dh_db *contigs, const char *reads_db_path, const char *pileups_path,
+                                  const int32_t *ranges2, int32_t nranges, const int64_t *rep_ptr, const int32_t *rep_iv,
+                                  const dh_process_opts *opts, int32_t only, int32_t sorted, dh_insertions **out,
+                                  int32_t **file_index, int32_t **skipped, int32_t *nskipped);
 void dh_chaindb_destroy(dh_chaindb *d);
 int32_t dh_chaindb_npiles(const dh_chaindb *d);
 const int32_t *dh_chaindb_pile_counts(const dh_chaindb *d);

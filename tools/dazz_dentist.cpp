@@ -518,3 +518,248 @@ int tool_filter_mask(const Args &args)
     must(write_mask(pos[0], pos[2], ncontigs, dh_mask_set_ptr(res.get()), dh_mask_set_iv(res.get()), dh_mask_set_count(res.get())));
     return 0;
 }
+
+// ---------------------------------------------------------------------------------- process, process-pile-ups
+// process [options] <ref-db> <reads-db> <pile-ups.db> <insertions.db>
+// `dentist process` / `dentist process-pile-ups` (commands/processPileUps/package.d:123-159; the options of
+// DentistCommand.processPileUps, commandline.d:1048-1054, 1088-1101, 1171-1281 and the other blocks that name it;
+// snakemake/Snakefile:1292-1334): the batches of <pile-ups.db> through dh_process_pileups_db_batches -- only the reads the
+// pile-ups name are loaded from <reads-db>, which is never opened whole -- and the closed pile-ups written sorted to
+// <insertions.db> with the trace spacing of the pile-up alignments.  Everything that fails before the batches are known
+// fails before a device is opened.
+namespace {
+const char *const kProcessUsage =
+    "usage: process [--mask=<name>[,<name>...]]... [--batch=<idx-spec>[,<idx-spec>...]]... [--min-anchor-length=<n>] "
+    "[--min-reads-per-pile-up=<n>] [--max-insertion-error=<f>] [--max-alignment-error=<f>] [--bad-fraction=<f>] "
+    "[--proper-alignment-allowance=<n>] [--min-relative-score=<f>] [--only=spanning|extending|both] <ref-db> <reads-db> "
+    "<pile-ups.db> <insertions.db>";
+
+// <idx> | <from>..<to> | <from>..$ (parsePileUpIdxSpec, commandline.d:1195-1215); an end of -1 stands for `$`
+bool parse_idx_spec(const std::string &spec, long long &from, long long &to)
+{
+    const char *p = spec.c_str();
+    char *end = nullptr;
+    if (!(*p >= '0' && *p <= '9')) return false;
+    from = strtoll(p, &end, 10);
+    if (*end == 0) {
+        to = from + 1;
+        return true;
+    }
+    if (end[0] != '.' || end[1] != '.') return false;
+    p = end + 2;
+    if (p[0] == '$' && p[1] == 0) {
+        to = -1;
+        return true;
+    }
+    if (!(*p >= '0' && *p <= '9')) return false;
+    to = strtoll(p, &end, 10);
+    return *end == 0;
+}
+
+const char *pile_status_name(int32_t st)
+{
+    static const char *const names[] = {"ok", "noCommonTracePoint", "tooSmall", "emptyAlignment", "flanksNotUnique", "orientation",
+                                        "maxInsertionError", "negativeInsertion", "alignOverflow", "unsupportedJoin"};
+    return st >= 0 && st < (int32_t)(sizeof(names) / sizeof(names[0])) ? names[st] : "unknown";
+}
+}  // namespace
+
+int tool_process(const Args &args)
+{
+    Args pos, masks;
+    std::string v_anchor, v_reads, v_ins, v_err, v_bad, v_allow, v_score;
+    std::vector<std::pair<long long, long long>> batches;
+    bool ignored = false;
+    int32_t only = 0;
+    auto add_masks = [&](const std::string &list) {  // <name>[,<name>...]
+        size_t at = 0;
+        while (at <= list.size()) {
+            const size_t comma = std::min(list.find(',', at), list.size());
+            if (comma > at) masks.push_back(list.substr(at, comma - at));
+            at = comma + 1;
+        }
+    };
+    auto add_batches = [&](const std::string &list) {
+        size_t at = 0;
+        while (at <= list.size()) {
+            const size_t comma = std::min(list.find(',', at), list.size());
+            long long from = 0, to = 0;
+            if (!parse_idx_spec(list.substr(at, comma - at), from, to)) fail("ill-formatted batch range");
+            batches.push_back({from, to});
+            at = comma + 1;
+        }
+    };
+    for (size_t i = 0; i < args.size(); i++) {
+        const std::string &a = args[i];
+        std::string v;
+        if ((a == "-m" || a == "-e" || a == "-b") && i + 1 < args.size()) {
+            if (a == "-m")
+                add_masks(args[++i]);
+            else if (a == "-b")
+                add_batches(args[++i]);
+            else
+                v_err = args[++i];
+        } else if (long_value(a, "--mask=", &v) || short_value(a, 'm', &v))
+            add_masks(v);
+        else if (long_value(a, "--batch=", &v) || short_value(a, 'b', &v))
+            add_batches(v);
+        else if (long_value(a, "--min-anchor-length=", &v_anchor) || long_value(a, "--min-reads-per-pile-up=", &v_reads) ||
+                 long_value(a, "--max-insertion-error=", &v_ins) || long_value(a, "--max-alignment-error=", &v_err) || short_value(a, 'e', &v_err) ||
+                 long_value(a, "--bad-fraction=", &v_bad) || long_value(a, "--proper-alignment-allowance=", &v_allow) ||
+                 long_value(a, "--min-relative-score=", &v_score))
+            continue;
+        else if (long_value(a, "--only=", &v)) {
+            if (v == "both")
+                only = 0;
+            else if (v == "spanning")
+                only = 1;
+            else if (v == "extending")
+                only = 2;
+            else
+                die("unknown or malformed option " + a + "\n" + kProcessUsage);
+        } else if (a == "--allow-single-reads")
+            fail("--allow-single-reads (single reads instead of a consensus) is not built");
+        else if (ignored_option(a) || short_value(a, 'A') || long_value(a, "--auxiliary-threads=") || long_value(a, "--aux-threads=") || short_value(a, 'P') ||
+                 long_value(a, "--tmpdir=") || a == "--keep-temp" || a == "-k" || long_value(a, "--daccord=") || long_value(a, "--daligner-consensus=") ||
+                 long_value(a, "--daligner-reads-vs-reads=") || long_value(a, "--daligner-self=") || long_value(a, "--datander-ref=") ||
+                 long_value(a, "--dust-reads="))
+            ignored = true;
+        else if (is_option(a))
+            die("unknown or malformed option " + a + "\n" + kProcessUsage);
+        else
+            pos.push_back(a);
+    }
+    if (masks.empty() || pos.size() != 4) die(kProcessUsage);  // (at least one mask: commandline.d:1789)
+    if (ignored)
+        notice_ignored("--config, -v, --quiet, -T / --threads, -A / --auxiliary-threads, -P / --tmpdir, --keep-temp and the pass-through options of "
+                       "the aligners");
+    dh_process_opts po;
+    dh_default_process_opts(&po);
+    po.max_reads = 0;  // (the reference knows minimum counts only, commandline.d:2125-2187)
+    double max_ins = 0.1, max_err = 0.3, bad_fraction = 0.08, min_score = 1.0;
+    int32_t allowance = -1;
+    lenient_number(v_anchor, &po.min_anchor), lenient_number(v_reads, &po.min_reads), lenient_number(v_ins, &max_ins), lenient_number(v_err, &max_err);
+    lenient_number(v_bad, &bad_fraction), lenient_number(v_allow, &allowance), lenient_number(v_score, &min_score);
+    if (!(max_err > 0 && max_err <= 0.3)) fail("--max-alignment-error must lie in (0, 0.3]");
+    if (!(max_ins >= 0 && max_ins <= 1)) fail("--max-insertion-error must lie in [0, 1]");
+    if (!(bad_fraction >= 0 && bad_fraction < 0.5)) fail("--bad-fraction must be within [0, 0.5)");
+    if (!(min_score > 0 && min_score <= 1)) fail("--min-relative-score must lie in (0, 1]");
+    if (po.min_anchor < 0 || po.min_reads < 1 || (!v_allow.empty() && allowance < 0)) fail("an option's value is out of range");
+    po.max_ins_err_ppm = (int32_t)llround(max_ins * 1e6), po.max_align_err_ppm = (int32_t)llround(max_err * 1e6);
+    po.bad_fraction_ppm = (int32_t)llround(bad_fraction * 1e6), po.min_relative_score_ppm = std::max<int32_t>((int32_t)llround(min_score * 1e6), 1);
+    // the batches against the file (validatePileUpBatches, commandline.d:1234-1271; without one: the whole file)
+    Handle<dh_chaindb, dh_chaindb_destroy> pdb;
+    must(dh_pileupdb_read(pos[2].c_str(), into(pdb)));
+    const long long npiles = dh_chaindb_npiles(pdb.get());
+    int32_t file_tspace = 0;
+    if (dh_chaindb_nseeded(pdb.get()) > 0) file_tspace = dh_chaindb_seeded(pdb.get())[0].tspace;
+    pdb.reset();
+    if (batches.empty()) batches.push_back({0, -1});
+    std::vector<int32_t> ranges;
+    for (size_t i = 0; i < batches.size(); i++) {
+        const long long from = batches[i].first, to = batches[i].second;
+        const bool whole_empty = npiles == 0 && from == 0 && to == -1;  // (an empty file has no valid range but the whole)
+        if (!whole_empty && !(from < (to < 0 ? npiles : to) && (to < 0 || to <= npiles)))
+            fail("invalid batch range; check that 0 <= <from> < <to> <= " + std::to_string(npiles));
+        ranges.push_back((int32_t)from);
+        ranges.push_back(to < 0 ? -1 : (int32_t)to);
+    }
+    for (size_t i = 0; i < batches.size(); i++)  // (validatePileUpBatchesDontIntersect, :1255-1271: the first pair in its order)
+        for (size_t j = i + 1; j < batches.size(); j++) {
+            const long long a1 = batches[i].second < 0 ? npiles : batches[i].second, b1 = batches[j].second < 0 ? npiles : batches[j].second;
+            if (std::max(batches[i].first, batches[j].first) < std::min(a1, b1))
+                fail("invalid --batch: <idx-spec>'s at indices " + std::to_string(i) + " and " + std::to_string(j) + " intersect");
+        }
+    po.allowance = allowance >= 0 ? allowance : (file_tspace > 0 ? file_tspace : po.allowance);
+    Dazz da;
+    must(dh_dazz_open(pos[0].c_str(), into(da)));
+    const int32_t ncontigs = dh_dazz_nreads(da.get());
+    std::vector<int64_t> mask_ptr;
+    std::vector<int32_t> mask_iv;
+    const std::string mask_err = read_united_masks(da.get(), pos[0], masks, mask_ptr, mask_iv);
+    if (!mask_err.empty()) fail(mask_err);
+    // the pile-ups are read before a device is asked for: a file that contradicts the reference fails here
+    {
+        Pileups probe;
+        LaSet probe_set;
+        for (size_t k = 0; k + 1 < ranges.size(); k += 2)
+            must(dh_pileups_from_db(pos[2].c_str(), ranges[k], ranges[k + 1] < 0 ? -1 : ranges[k + 1] - ranges[k], dh_dazz_offsets(da.get()), ncontigs,
+                                    into(probe), into(probe_set), nullptr));
+    }
+    Ctx ctx;
+    Db A;
+    Handle<dh_insertions, dh_insertions_destroy> ins;
+    int32_t *file_index = nullptr, *skipped = nullptr, nskipped = 0;
+    const bool need_device = npiles > 0;  // (an empty file: an empty insertions.db, and no device is asked for)
+    if (need_device) {
+        must(dh_ctx_create(0, nullptr, into(ctx)));
+        must(dh_db_create(ctx.get(), dh_dazz_bases(da.get()), dh_dazz_offsets(da.get()), ncontigs, nullptr, into(A)));
+        must(dh_process_pileups_db_batches(ctx.get(), A.get(), pos[1].c_str(), pos[2].c_str(), ranges.data(), (int32_t)ranges.size() / 2, mask_ptr.data(),
+                                           mask_iv.data(), &po, only, 1, into(ins), &file_index, &skipped, &nskipped));
+    }
+    for (int32_t k = 0; k < nskipped; k++)
+        fprintf(stderr, "process: pile-up %d skipped by --only=%s\n", skipped[k], only == 1 ? "spanning" : "extending");
+    const int32_t nrec = ins ? dh_insertions_count(ins.get()) : 0;
+    for (int32_t i = 0; i < nrec; i++) {
+        const int32_t st = dh_insertions_records(ins.get())[i].status;
+        if (st != DH_PILE_OK) fprintf(stderr, "process: pile-up %d not closed: %s\n", file_index[i], pile_status_name(st));
+    }
+    dh_shard_free(file_index);
+    dh_shard_free(skipped);
+    if (ins)
+        must(dh_insertions_write_db(ins.get(), dh_dazz_offsets(da.get()), ncontigs, po.tspace_pile, pos[3].c_str()));
+    else
+        must(dh_insertiondb_write(pos[3].c_str(), 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------- show-pile-ups
+// show-pile-ups [-j] <pile-ups.db>
+// `dentist show-pile-ups` (commands/showPileUps.d:46-115): the size of the file and the number of its pile-ups, read
+// alignments, seeded alignments, local alignments and trace points (pairs), as the table of :105-115 or with -j / --json as one
+// JSON object (the Snakefile sizes the batches of `process` from it).  The whitespace of the JSON is not pinned.  Host only.
+int tool_show_pile_ups(const Args &args)
+{
+    const char *usage = "usage: show-pile-ups [-j] [--config=<file>] [-v] [--quiet] [-T<n>] <pile-ups.db>";
+    Args pos;
+    bool json = false, ignored = false;
+    for (const std::string &a : args) {
+        if (a == "-j" || a == "--json")
+            json = true;
+        else if (ignored_option(a))
+            ignored = true;
+        else if (is_option(a))
+            die("unknown or malformed option " + a + "\n" + usage);
+        else
+            pos.push_back(a);
+    }
+    if (pos.size() != 1) die(usage);
+    if (ignored) notice_ignored();
+    FILE *f = fopen(pos[0].c_str(), "rb");
+    if (!f) fail("cannot open " + pos[0]);
+    fseek(f, 0, SEEK_END);
+    const long long size = ftell(f);
+    fclose(f);
+    Handle<dh_chaindb, dh_chaindb_destroy> db;
+    must(dh_pileupdb_read(pos[0].c_str(), into(db)));
+    const char *const key[6] = {"totalDbSize", "numPileUps", "numReadAlignments", "numSeededAlignments", "numLocalAlignments", "numTracePoints"};
+    const long long val[6] = {size,
+                              dh_chaindb_npiles(db.get()),
+                              dh_chaindb_nread_alignments(db.get()),
+                              (long long)dh_chaindb_nseeded(db.get()),
+                              (long long)dh_chaindb_nlas(db.get()),
+                              (long long)dh_chaindb_ntrace(db.get()) / 2};  // (the container counts u16 values, the reference pairs)
+    if (json) {
+        printf("{");
+        for (int i = 0; i < 6; i++) printf("%s\"%s\":%lld", i ? "," : "", key[i], val[i]);
+        printf("}\n");
+        return 0;
+    }
+    const long long most = *std::max_element(val, val + 6);
+    const int width = most > 0 ? (int)std::ceil(std::log10((double)most)) : 0;  // (columnWidth, :88-102: log10 rounded up)
+    for (int i = 0; i < 6; i++) {
+        const std::string label = std::string(key[i]) + ":";
+        printf("%-20s %*lld%s\n", label.c_str(), width, val[i], i == 0 ? " bytes" : "");
+    }
+    return 0;
+}

@@ -34,6 +34,8 @@ int tool_collect(const Args &args);
 int tool_mask_repetitive_regions(const Args &args);
 int tool_merge_masks(const Args &args);
 int tool_filter_mask(const Args &args);
+int tool_process(const Args &args);        // (these two are reached through tools/process, whose main is in dazz_process.cpp)
+int tool_show_pile_ups(const Args &args);
 // dazz_check.cpp
 int tool_check_results(const Args &args);
 // dazz_output.cpp: `output`, an executable of its own (its main is there)
