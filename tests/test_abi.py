@@ -34,6 +34,54 @@ def test_library_exports_every_declared_symbol():
     assert L.dh_abi_version() == 4
 
 
+def declared_signatures():
+    """name -> (result, [parameters]) of every dh_* function include/*.h declares, as C text without comments"""
+    sigs = {}
+    for h in glob.glob(os.path.join(ROOT, "include", "*.h")):
+        txt = re.sub(r"/\*.*?\*/", "", open(h).read(), flags=re.S)
+        txt = "\n".join(l for l in txt.split("\n") if not l.lstrip().startswith("#"))
+        for res, name, args in re.findall(r"(?:^|[;}])\s*((?:\w+\s+)*\w+[\s*]+)(dh_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt, flags=re.M):
+            if not res.split()[0] == "typedef":
+                sigs[name] = (res.strip(), [] if args.strip() == "void" else [a.strip() for a in args.split(",")])
+    return sigs
+
+
+def c_class(decl, result=False):
+    """pointer, 32-bit integer, 64-bit integer or double (void as a result: None) of a C parameter or result type"""
+    if "*" in decl or "dh_remap_fn" in decl:
+        return "pointer"
+    ty = [w for w in decl.split() if w != "const"][0 if result else -2]
+    return {"void": None, "int": "i32", "int32_t": "i32", "int64_t": "i64", "double": "double"}[ty]
+
+
+def ctypes_class(t):
+    if t is None:
+        return None
+    if t in (ctypes.c_int, ctypes.c_int32):
+        return "i32"
+    if t is ctypes.c_int64:
+        return "i64"
+    if t is ctypes.c_double:
+        return "double"
+    assert t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, (ctypes._Pointer, ctypes._CFuncPtr)), t
+    return "pointer"
+
+
+def test_prototypes_match_the_header():
+    """Every declared function has a prototype on the loaded library, and its argument count, the class of every parameter
+    (pointer, 32-bit integer, 64-bit integer, double) and the class of its result are the header's."""
+    L = dentist_amd.lib()
+    sigs = declared_signatures()
+    assert set(sigs) == declared_symbols() and len(sigs) == len(_lib.SYMBOLS)
+    for name in _lib.SYMBOLS:
+        fn = getattr(L, name)
+        assert fn.argtypes is not None, f"{name} has no prototype"
+        res, args = sigs[name]
+        assert len(fn.argtypes) == len(args), name
+        assert [ctypes_class(t) for t in fn.argtypes] == [c_class(a) for a in args], name
+        assert ctypes_class(fn.restype) == c_class(res, result=True), name
+
+
 def test_process_opts_layout_matches_the_abi_version():
     """dh_process_opts grew by two int32 fields with ABI 4 (max_partners, min_relative_score_ppm): the binding's struct is
     the header's (16 x int32 = 64 bytes), the defaults fill the new fields, and a zero there is refused."""
