@@ -37,7 +37,6 @@ int dh_fail(int code, const std::string &msg);
 #include <memory>
 #include <utility>
 #include <vector>
-struct dh_scaffold;
 // a vector whose resize() leaves trivially constructible elements unwritten: the gathered records of a plan are written
 // once by the host threads (a value-initialising resize was 2.2 of the plan's 6.3 ms: 14 MB of first-touch page faults on
 // one thread)
@@ -56,11 +55,7 @@ struct dh_noinit_alloc : std::allocator<T> {
             ::new ((void *)p) U(std::forward<A>(a)...);
     }
 };
-typedef std::vector<dh_la, dh_noinit_alloc<dh_la>> dh_la_vec;
-// dh_scaffold.cpp: the scaffold of the gathered join blobs of the sharded collector (glas: two LA records per join)
-int dh_scaffold_from_join_blobs(const uint8_t *const *blobs, const int64_t *sizes, int32_t world, int32_t ncontigs,
-                                const int32_t *input_gaps, int32_t ngaps, const struct dh_scaffold_opts *opts,
-                                dh_la_vec &glas, dh_scaffold **out);
+typedef std::vector<dh_la, dh_noinit_alloc<dh_la>> dh_la_vec;  // (the plan of the sharded collector: dh_shard.cpp, dh_scaffold.h)
 // allocate total + 2 * DB_PAD bytes filled with code 4; *base = alloc + DB_PAD
 int dh_alloc_bases(hipStream_t st, int64_t total, uint8_t **alloc, uint8_t **base, bool pads_only = false);
 

@@ -9,6 +9,7 @@
 
 #include "dh_process.h"
 #include "dh_parallel.h"
+#include "dh_scaffold.h"
 
 // ------------------------------------------------------------------------------------ sharded collect + process
 //
@@ -132,13 +133,7 @@ extern "C" int dh_shard_graph_plan_create(const uint8_t *const *blobs, const int
                                           const dh_process_opts *opts, dh_shard_plan **out)
 {
     if (!opts || !out) return dh_fail(DH_EINVAL, "dh_shard_graph_plan_create: bad argument");
-    auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char *w) {
-        if (!getenv("DH_TRACE")) return;
-        const auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "[graph plan] %-20s %.2f ms\n", w, std::chrono::duration<double, std::milli>(t - t0).count());
-        t0 = t;
-    };
+    dh_lap_timer lap{"[graph plan]", 20};
     dh_shard_plan *p = new dh_shard_plan();
     dh_scaffold *sc = nullptr;
     if (int rc = dh_scaffold_from_join_blobs(blobs, sizes, world, ncontigs, input_gaps, ngaps, sopts, p->las, &sc)) {
