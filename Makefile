@@ -8,7 +8,7 @@ SIM := dentist_amd/sim/libdh_sim.so
 
 DAZZ_TOOLS := fasta2DB fasta2DAM DBsplit DBrm DBdump DBshow DBdust LAmerge DAScover DASqv computeintrinsicqv daccord merge-insertions LAsplit Catrack TANmask LApaf LAtranspose DBnw stretcher fm-index chain-local-alignments propagate-mask validate-regions collect mask-repetitive-regions merge-masks filter-mask check-results
 PROCESS_TOOLS := process process-pile-ups show-pile-ups
-TOOLS := tools/daligner tools/damapper tools/datander tools/dazz_tools $(addprefix tools/,$(DAZZ_TOOLS)) tools/output $(addprefix tools/,$(PROCESS_TOOLS))
+TOOLS := tools/daligner tools/damapper tools/datander tools/dazz_tools $(addprefix tools/,$(DAZZ_TOOLS)) tools/output $(addprefix tools/,$(PROCESS_TOOLS)) tools/bed2mask
 
 all: $(LIB) $(SIM) oracle $(TOOLS)
 
@@ -42,6 +42,10 @@ tools/process: $(PROCESS_SRCS) tools/dazz_tools.h tools/cli.h include/dentist_hi
 
 tools/process-pile-ups tools/show-pile-ups: tools/process
 	cp $< $@
+
+# `dentist bed2mask`: host only, a program of its own for the same reason as tools/output
+tools/bed2mask: tools/dazz_bed2mask.cpp tools/cli.h include/dentist_hip.h $(LIB)
+	$(HIPCC) -O2 -std=c++17 -o $@ tools/dazz_bed2mask.cpp -Ldentist_amd -ldentist_hip -Wl,-rpath,'$$ORIGIN/../dentist_amd'
 
 # one object per translation unit (build/ is git-ignored): `make -j8` rebuilds only what changed
 OBJDIR := build/obj
@@ -216,3 +220,10 @@ tests/native/libbpsload_host.so: tests/native/bpsload_host.cpp dentist_amd/csrc/
 # the ends of a chunk are where this code would overrun
 tests/native/bpsload_host_san: tests/native/bpsload_host_main.cpp tests/native/bpsload_host.cpp dentist_amd/csrc/dh_bpsload.h
 	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/bpsload_host_main.cpp tests/native/bpsload_host.cpp
+
+# the BED parser (dentist_amd/csrc/dh_bedmask.cpp) and the DAZZ_DB files with their track extras (dentist_amd/csrc/dazzdb.cpp),
+# both host code, with a stand-alone main under the host sanitizers (a program of its own: nothing is preloaded); run it once
+# after a change to either -- the last field of a line, a line without its newline and an extra cut at any byte are where this
+# code would overrun
+tests/native/bedmask_host_san: tests/native/bedmask_host_main.cpp dentist_amd/csrc/dh_bedmask.cpp dentist_amd/csrc/dazzdb.cpp dentist_amd/csrc/dh_dazzfmt.h include/dentist_hip.h
+	g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -o $@ tests/native/bedmask_host_main.cpp dentist_amd/csrc/dh_bedmask.cpp dentist_amd/csrc/dazzdb.cpp

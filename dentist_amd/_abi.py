@@ -417,6 +417,18 @@ _PROTOTYPES = {
     "dh_dazz_header": (cstr, [vp, i32]),
     "dh_dazz_read_mask": (i64, [vp, cstr, cstr, vp, vp, i64]),
     "dh_dazz_write_mask": (cint, [cstr, cstr, i32, vp, vp]),
+    # ---- track extras, BED -> mask
+    "dh_dazz_read_extra": (i64, [cstr, cstr, cstr, P(i32), P(i32), vp, i64]),
+    "dh_dazz_write_extra": (cint, [cstr, cstr, cstr, i32, i32, vp, i64]),
+    "dh_bed_to_mask": (cint, [vp, cstr, i64, cstr, i32, P(vp)]),
+    "dh_bed_mask_destroy": (None, [vp]),
+    "dh_bed_mask_ncontigs": (i32, [vp]),
+    "dh_bed_mask_count": (i64, [vp]),
+    "dh_bed_mask_ptr": (vp, [vp]),
+    "dh_bed_mask_iv": (vp, [vp]),
+    "dh_bed_mask_contig_ids": (vp, [vp]),
+    "dh_bed_mask_read_off": (vp, [vp]),
+    "dh_bed_mask_read_ids": (vp, [vp]),
     # ---- the binary containers between DENTIST's commands
     "dh_pileupdb_write": (cint, [cstr, i32, vp, vp, vp, vp, vp]),
     "dh_pileupdb_read": (cint, [cstr, P(vp)]),

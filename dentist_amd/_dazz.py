@@ -1,4 +1,6 @@
-"""Files: DAZZ_DB databases and their mask tracks, the read loader, and DENTIST's pile-ups.db and insertions.db."""
+"""Files: DAZZ_DB databases, their mask tracks and the extras of a mask track, BED to mask, the read loader, and DENTIST's
+pile-ups.db and insertions.db."""
+import collections
 import ctypes
 
 import numpy as np
@@ -67,6 +69,57 @@ def dazz_write_mask(db_path, name, ptr, iv):
     p = np.ascontiguousarray(ptr, dtype=np.int64)
     v = np.ascontiguousarray(iv, dtype=np.int32)
     _check(lib().dh_dazz_write_mask(db_path.encode(), name.encode(), len(p) - 1, p.ctypes.data, v.ctypes.data))
+
+
+ENOTFOUND = -7                    # DH_ENOTFOUND: the mask has no extra of that name
+ACCUM_MODES = ("exact", "sum")    # DH_ACCUM_EXACT, DH_ACCUM_SUM
+MaskExtra = collections.namedtuple("MaskExtra", "data accum")   # data: int64 or float64 (the vtype), accum: "exact" | "sum"
+BedMask = collections.namedtuple("BedMask", "ptr iv contig_ids read_off read_ids")
+
+
+def read_mask_extra(db_path, mask, name, dtype=None):
+    """dh_dazz_read_extra: the first track extra `name` of mask `mask` as MaskExtra(data, accum), None when the mask has none of
+    that name.  dtype np.int64 / np.float64 asks for that value type (another one stored is a DhError), None takes either."""
+    L = lib()
+    want = -1 if dtype is None else {"int64": 0, "float64": 1}[np.dtype(dtype).name]
+    vtype, accum = ctypes.c_int32(want), ctypes.c_int32(0)
+    args = (db_path.encode(), mask.encode(), name.encode(), ctypes.byref(vtype), ctypes.byref(accum))
+    n = L.dh_dazz_read_extra(*args, None, 0)
+    if n == ENOTFOUND:
+        return None
+    if n < 0:
+        _check(int(n))
+    data = np.zeros(n, dtype=np.float64 if vtype.value == 1 else np.int64)
+    m = L.dh_dazz_read_extra(*args, data.ctypes.data, n)
+    if m < 0:
+        _check(int(m))
+    return MaskExtra(data, ACCUM_MODES[accum.value])
+
+
+def write_mask_extra(db_path, mask, name, data, accum="exact"):
+    """dh_dazz_write_extra: `data` (integers as int64, anything else as float64) appended to the mask as the extra `name`."""
+    a = np.asarray(data)
+    a = np.ascontiguousarray(a, dtype=np.int64 if a.dtype.kind in "iub" else np.float64)
+    _check(lib().dh_dazz_write_extra(db_path.encode(), mask.encode(), name.encode(), int(a.dtype == np.float64),
+                                     ACCUM_MODES.index(accum), a.ctypes.data, len(a)))
+
+
+def bed_to_mask(db, bed_text, bed_name="-", data_comments=False):
+    """dh_bed_to_mask: the BED text against the opened DazzDb `db` (the whole .dam) as BedMask(ptr, iv, contig_ids, read_off,
+    read_ids): the mask as read_mask returns it, contig_ids int64[count, 2], the read ids of interval i at
+    read_ids[read_off[i]:read_off[i + 1]]."""
+    L = lib()
+    b = bed_text.encode() if isinstance(bed_text, str) else bed_text
+    h = ctypes.c_void_p()
+    _check(L.dh_bed_to_mask(db._h, b, len(b), bed_name.encode(), int(data_comments), ctypes.byref(h)))
+    try:
+        n = L.dh_bed_mask_count(h)
+        read_off = copy(L.dh_bed_mask_read_off(h), n + 1, np.int64)
+        return BedMask(copy(L.dh_bed_mask_ptr(h), L.dh_bed_mask_ncontigs(h) + 1, np.int64), copy(L.dh_bed_mask_iv(h), 2 * n, np.int32),
+                       copy(L.dh_bed_mask_contig_ids(h), (n, 2), np.int64), read_off,
+                       copy(L.dh_bed_mask_read_ids(h), int(read_off[-1]), np.int64))
+    finally:
+        L.dh_bed_mask_destroy(h)
 
 
 def load_reads(ctx, path, ids):

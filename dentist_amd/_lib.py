@@ -8,7 +8,7 @@ The facade over the modules the binding is made of, one per role:
   _process  Pileups, map_reads, Cropped, the process calls, the scaffold graph
   _shard    Comm, ShardPlan, shard_*
   _output   the output calls
-  _dazz     DazzDb, load_reads, pile-ups.db and insertions.db
+  _dazz     DazzDb, mask track extras, bed_to_mask, load_reads, pile-ups.db and insertions.db
   _context  Context: a docstring and a one-line call per command
 """
 from ._abi import (AlignOpts, AlignStats, ChainOpts, CumStats, DhError, MaskOpts, OutputFilter, OutputOpts,  # noqa: F401
@@ -28,9 +28,9 @@ from ._process import (Cropped, Pileups, _take_insertions, consensus, default_pr
 from ._shard import (Comm, ShardPlan, shard_pack_candidates, shard_pack_cropped, shard_read_joins, shard_run,  # noqa: F401
                      shard_run_prepare, shard_unpack_cropped)
 from ._output import JOIN_POLICIES, output_assembly, output_fasta, output_plan  # noqa: F401
-from ._dazz import (DazzDb, dazz_create_dam, dazz_create_db, dazz_split, dazz_write_mask, insertiondb_merge,  # noqa: F401
-                    insertiondb_read, insertiondb_write, insertions_from_db, load_reads, load_stats, pileupdb_read,
-                    pileupdb_write, pileups_from_db)
+from ._dazz import (BedMask, DazzDb, MaskExtra, bed_to_mask, dazz_create_dam, dazz_create_db, dazz_split,  # noqa: F401
+                    dazz_write_mask, insertiondb_merge, insertiondb_read, insertiondb_write, insertions_from_db, load_reads,
+                    load_stats, pileupdb_read, pileupdb_write, pileups_from_db, read_mask_extra, write_mask_extra)
 from ._context import Context  # noqa: F401
 
 

@@ -539,6 +539,90 @@ extern "C" int64_t dh_dazz_read_mask(const dh_dazz *db, const char *db_path, con
     return n;
 }
 
+// ---------------------------------------------------------------------------------- track extras
+// source/dentist/dazzler.d:5173-5344 (DazzExtra / readDazzExtra / writeDazzExtra): behind the header and the nreads + 1
+// pointers of a mask's .anno come any number of extras -- int32 vtype (0 int64, 1 double), int32 length, int32 accum
+// (0 exact, 1 sum), int32 name length, the name without a NUL, `length` values of 8 bytes.  No reader of the mask itself
+// looks behind the pointers, and dh_dazz_write_mask truncates the file: rewriting a mask drops its extras, as in the reference.
+namespace {
+std::string extra_anno(const Paths &p, const char *mask) { return p.hidden((std::string(mask) + ".anno").c_str()); }
+}  // namespace
+
+extern "C" int64_t dh_dazz_read_extra(const char *db_path, const char *mask, const char *name, int32_t *vtype, int32_t *accum,
+                                      void *data, int64_t cap)
+{
+    Paths p;
+    if (!db_path || !mask || !name || !vtype || !split_path(std::string(db_path), p, true)) return dh_fail(DH_EIO, "DAZZ_DB not found");
+    if (*vtype < -1 || *vtype > 1) return dh_fail(DH_EINVAL, "dh_dazz_read_extra: vtype must be 0 (int64), 1 (double) or -1 (any)");
+    const std::string file = extra_anno(p, mask);
+    FILE *an = fopen(file.c_str(), "rb");
+    if (!an) return dh_fail(DH_EIO, std::string("mask track not found: ") + mask);
+    struct Closer {
+        FILE *f;
+        ~Closer() { fclose(f); }
+    } closer{an};
+    int64_t index = 0;
+    auto bad = [&](const std::string &what) {
+        return dh_fail(DH_EINVAL, "error while reading mask extra `" + file + "." + name + "` (current extra index " + std::to_string(index) +
+                                      "): " + what);
+    };
+    fseek(an, 0, SEEK_END);
+    const int64_t size = (int64_t)ftell(an);
+    rewind(an);
+    int32_t head[2] = {0, 0};
+    if (fread(head, 4, 2, an) != 2 || head[0] < 0) return bad("unexpected end of file while reading the mask header");
+    int64_t at = 8 + 8 * ((int64_t)head[0] + 1);
+    if (at > size) return bad("unexpected end of file while reading the mask pointers");
+    const size_t name_len = strlen(name);
+    std::string cur;
+    for (;; index++) {
+        if (at == size) return dh_fail(DH_ENOTFOUND, "mask " + std::string(mask) + " has no extra named " + name);
+        int32_t h[4];
+        if (size - at < 16) return bad("unexpected end of file while reading header data");
+        if (fseek(an, (long)at, SEEK_SET) != 0 || fread(h, 4, 4, an) != 4) return bad("unexpected end of file while reading header data");
+        at += 16;
+        if (h[1] < 0 || h[3] < 0) return bad("negative length");
+        if ((int64_t)h[3] > size - at) return bad("unexpected end of file while reading name");
+        cur.resize((size_t)h[3]);
+        if (h[3] > 0 && fread(&cur[0], 1, cur.size(), an) != cur.size()) return bad("unexpected end of file while reading name");
+        at += h[3];
+        if (8 * (int64_t)h[1] > size - at) return bad("unexpected end of file while reading data");
+        if (cur.size() != name_len || memcmp(cur.data(), name, name_len) != 0) {
+            at += 8 * (int64_t)h[1];
+            continue;
+        }
+        if (h[0] != 0 && h[0] != 1) return bad("unknown vtype " + std::to_string(h[0]));
+        if (*vtype >= 0 && h[0] != *vtype)
+            return bad("vtype does not match: expected " + std::to_string(*vtype) + " but got " + std::to_string(h[0]));
+        if (h[2] != 0 && h[2] != 1) return bad("unknown accumulation mode " + std::to_string(h[2]));
+        *vtype = h[0];
+        if (accum) *accum = h[2];
+        const int64_t take = data ? std::min<int64_t>(h[1], std::max<int64_t>(cap, 0)) : 0;
+        if (take > 0 && fread(data, 8, (size_t)take, an) != (size_t)take) return bad("unexpected end of file while reading data");
+        return h[1];
+    }
+}
+
+extern "C" int dh_dazz_write_extra(const char *db_path, const char *mask, const char *name, int32_t vtype, int32_t accum,
+                                   const void *data, int64_t n)
+{
+    Paths p;
+    if (!db_path || !mask || !name || !split_path(std::string(db_path), p, true)) return dh_fail(DH_EIO, "DAZZ_DB not found");
+    if ((vtype != 0 && vtype != 1) || (accum != 0 && accum != 1) || n < 0 || n > INT32_MAX || (n > 0 && !data) || strchr(mask, '/'))
+        return dh_fail(DH_EINVAL, "dh_dazz_write_extra: bad argument");
+    const std::string file = extra_anno(p, mask);
+    FILE *an = fopen(file.c_str(), "rb");
+    if (!an) return dh_fail(DH_EIO, std::string("mask track not found: ") + mask);
+    fclose(an);
+    an = fopen(file.c_str(), "ab");  // appended whatever the file holds already (dazzler.d:5324-5326)
+    if (!an) return dh_fail(DH_EIO, "cannot append to " + file);
+    const int32_t h[4] = {vtype, (int32_t)n, accum, (int32_t)strlen(name)};
+    bool ok = fwrite(h, 4, 4, an) == 4;
+    if (h[3] > 0) ok = ok && fwrite(name, 1, (size_t)h[3], an) == (size_t)h[3];
+    if (n > 0) ok = ok && fwrite(data, 8, (size_t)n, an) == (size_t)n;
+    ok = (fclose(an) == 0) && ok;
+    return ok ? DH_OK : dh_fail(DH_EIO, "short write of " + file);
+}
 
 // ---------------------------------------------------------------------------------- byte tracks
 // Per-read byte vectors (`qual` / `inqual`: one intrinsic QV per trace tile, written by DASqv /

@@ -1404,6 +1404,56 @@ int64_t dh_dazz_read_mask(const dh_dazz *db, const char *db_path, const char *na
                           int64_t iv_cap);
 int dh_dazz_write_mask(const char *db_path, const char *name, int32_t nreads, const int64_t *ptr,
                        const int32_t *iv);
+/* track extras (source/dentist/dazzler.d:5173-5344): named vectors of int64 or double stored behind the nreads + 1 pointers
+ * of a mask's .anno, any number of them -- int32 vtype (DH_EXTRA_INT64 / DH_EXTRA_DOUBLE), int32 length, int32 accum
+ * (DH_ACCUM_EXACT / DH_ACCUM_SUM: how Catrack would combine block tracks), int32 name length, the name without a NUL, `length`
+ * values of 8 bytes.  Host only.  No reader of a mask looks behind the pointers; dh_dazz_write_mask truncates the .anno, so
+ * rewriting a mask drops its extras (the reference does the same).
+ *   read: the first extra called `name`, the ones before it skipped by their lengths.  *vtype on entry is the type asked for
+ *      (-1: either), on return the type stored; *accum (may be NULL) the stored mode.  data may be NULL to size, cap counts
+ *      elements; returns the element count.  DH_ENOTFOUND: the track has no extra of that name -- no error for a caller to whom
+ *      extras are optional.  DH_EINVAL naming the file and the index of the extra: a file that ends inside an extra's header,
+ *      name or data, another vtype than the one asked for, an unknown vtype or mode.  DH_EIO: no such track.
+ *   write: appends, whatever the file holds already (a second extra of one name is never found by read). */
+#define DH_ENOTFOUND (-7)
+#define DH_EXTRA_INT64 0
+#define DH_EXTRA_DOUBLE 1
+#define DH_ACCUM_EXACT 0
+#define DH_ACCUM_SUM 1
+int64_t dh_dazz_read_extra(const char *db_path, const char *mask, const char *name, int32_t *vtype, int32_t *accum, void *data,
+                           int64_t cap);
+int dh_dazz_write_extra(const char *db_path, const char *mask, const char *name, int32_t vtype, int32_t accum, const void *data,
+                        int64_t n);
+
+/* ---- BED -> mask (host only): `dentist bed2mask` (source/dentist/commands/bed2mask.d:92-287), the intervals of a BED file in
+ *      scaffold coordinates as a mask of the contigs of the opened .dam, with the contig pair and the read ids a data comment
+ *      (`contigs-<a>-<b>|reads-<id>-<id>...`, column 4 as dh_output_assembly writes it to --closed-gaps-bed) gives every line.
+ *   Input.  db: the whole opened .dam; its scaffolds are the runs of contigs under one header with ascending contig numbers,
+ *      keyed by the header without '>' up to the first tab, a contig covering [fpulse, fpulse + length) of its scaffold.
+ *      bed[n]: the text; bed_name: what messages call it.  data_comments 0: column 4 is not looked at.
+ *   Rules.  Empty lines are skipped; columns are split at tabs; columns 2 and 3 are begin and end.  A line gives one interval
+ *      per contig of its scaffold left after dropping the leading contigs with end <= begin and the trailing ones with begin >=
+ *      end, clipped to the contig and shifted to its coordinates; every interval of a line carries the line's ids.  Data
+ *      comment: parts split at '|', fields at '-'; `contigs` needs exactly two ids, `reads` takes any number, other parts are
+ *      ignored, a later part of a name overwrites an earlier one; ids are plain decimal digits up to 2^32 - 1.  All errors of a
+ *      line come together: "ill-formatted data comment in BED file <name>:<line>:" and one "  - " line each.
+ *   Result.  The mask in the layout of dh_dazz_read_mask (ptr[ncontigs + 1], (begin, end) pairs in file order), per interval
+ *      the contig-id pair (contig_ids[2 * i], [2 * i + 1]; 0 0 without data comments) and the read ids read_ids[read_off[i] ..
+ *      read_off[i + 1]).  Nothing is sorted or merged: the ids are positional.
+ *   Refusals beyond the reference, DH_EINVAL naming <name>:<line>: an unknown scaffold, fewer than three columns, a coordinate
+ *      that is not a decimal number below 2^31, begin > end, an interval that overlaps no contig, an interval that sorts before
+ *      the one in front of it by (contig, begin, end) (the reference sorts the mask but not the ids), and with data_comments a
+ *      line without a `contigs` part. */
+typedef struct dh_bed_mask dh_bed_mask;
+int dh_bed_to_mask(const dh_dazz *db, const char *bed, int64_t n, const char *bed_name, int32_t data_comments, dh_bed_mask **out);
+void dh_bed_mask_destroy(dh_bed_mask *m);
+int32_t dh_bed_mask_ncontigs(const dh_bed_mask *m);
+int64_t dh_bed_mask_count(const dh_bed_mask *m);
+const int64_t *dh_bed_mask_ptr(const dh_bed_mask *m);        /* ncontigs + 1 */
+const int32_t *dh_bed_mask_iv(const dh_bed_mask *m);         /* 2 x count (never NULL) */
+const int64_t *dh_bed_mask_contig_ids(const dh_bed_mask *m); /* 2 x count */
+const int64_t *dh_bed_mask_read_off(const dh_bed_mask *m);   /* count + 1 */
+const int64_t *dh_bed_mask_read_ids(const dh_bed_mask *m);   /* read_off[count] (never NULL) */
 
 /* ---- the binary containers between DENTIST's commands (host only):
  *      pile-ups.db (collect -> process, source/dentist/common/binio/pileupdb.d:400-897) and

@@ -175,6 +175,19 @@ inline std::string read_mask(const dh_dazz *da, const std::string &db_path, cons
     return "";
 }
 
+// The int64 track extra `name` of mask `mask`: false when the mask has no extra of that name, exit 2 on anything else.
+inline bool read_extra(const std::string &db_path, const std::string &mask, const char *name, std::vector<int64_t> &data)
+{
+    int32_t vtype = DH_EXTRA_INT64;
+    const int64_t cnt = dh_dazz_read_extra(db_path.c_str(), mask.c_str(), name, &vtype, nullptr, nullptr, 0);
+    if (cnt == DH_ENOTFOUND) return false;
+    if (cnt < 0) fail("mask " + mask + ": " + dh_last_error());
+    data.assign((size_t)cnt + 1, 0);  // (never an empty array)
+    if (dh_dazz_read_extra(db_path.c_str(), mask.c_str(), name, &vtype, nullptr, data.data(), cnt) != cnt) fail("mask " + mask + ": " + dh_last_error());
+    data.resize((size_t)cnt);
+    return true;
+}
+
 // the intervals of every contig sorted, intersecting or touching ones merged (iv may come out empty: the caller that hands
 // it to the library appends an element)
 inline void merge_intervals(std::vector<std::vector<std::pair<int32_t, int32_t>>> &per, std::vector<int64_t> &ptr, std::vector<int32_t> &iv)

@@ -131,7 +131,8 @@ int tool_propagate_mask(const Args &args)
 //                  <ref-db> <reads-db> <in.las> <regions-mask>
 // One JSON line per invalid region (per region with --report-all) of the mask <regions-mask> of <ref-db>, the weak-coverage
 // mask written on request (dh_la_validate_regions: `dentist validate-regions`, commands/validateRegions.d:141-512;
-// snakemake/Snakefile:1425-1466).
+// snakemake/Snakefile:1425-1466).  A mask that carries the track extras `contigs` and `reads` (bed2mask --data-comments) also
+// gives every region its contig pair and consensus read ids, which the workflow's skip-gaps file is made from.
 int tool_validate_regions(const Args &args)
 {
     const char *usage = "usage: validate-regions [--min-coverage-reads=<n> | --read-coverage=<f> --ploidy=<n>] [--min-spanning-reads=<n>] "
@@ -184,9 +185,37 @@ int tool_validate_regions(const Args &args)
     std::vector<int32_t> iv;
     const std::string mask_err = read_mask(da.get(), pos[0], pos[3], ptr, iv);
     if (!mask_err.empty()) fail(mask_err);
+    // the track extras `contigs` and `reads` of the mask, where bed2mask --data-comments stored them (:204-256): positional,
+    // one pair and one list per interval of the whole mask
+    std::vector<int64_t> contig_ids, read_ids, read_off;
+    const bool has_contigs = read_extra(pos[0], pos[3], "contigs", contig_ids), has_reads = read_extra(pos[0], pos[3], "reads", read_ids);
+    const int64_t nmask = ptr[(size_t)ncontigs];
+    if (has_contigs && (int64_t)contig_ids.size() != 2 * nmask)
+        fail("mask " + pos[3] + ": the extra `contigs` has " + std::to_string(contig_ids.size()) + " entries, not two for each of the " +
+             std::to_string(nmask) + " intervals of the mask (<ref-db> must be the whole DB)");
+    if (has_reads) {  // per interval the count, then the ids
+        std::vector<int64_t> ids;
+        read_off.push_back(0);
+        for (size_t at = 0; at < read_ids.size();) {
+            const int64_t k = read_ids[at++];
+            if (k < 0 || k > (int64_t)(read_ids.size() - at)) fail("mask " + pos[3] + ": the extra `reads` ends inside a list of read ids");
+            ids.insert(ids.end(), read_ids.begin() + (ptrdiff_t)at, read_ids.begin() + (ptrdiff_t)(at + (size_t)k));
+            at += (size_t)k;
+            read_off.push_back((int64_t)ids.size());
+        }
+        if ((int64_t)read_off.size() - 1 != nmask)
+            fail("mask " + pos[3] + ": the extra `reads` holds " + std::to_string(read_off.size() - 1) + " lists, not one for each of the " +
+                 std::to_string(nmask) + " intervals of the mask (<ref-db> must be the whole DB)");
+        read_ids.swap(ids);
+    }
+    // ... sliced with the regions (:259-271)
     std::vector<dh_region> regions;
+    std::vector<int64_t> region_interval;
     for (int32_t c = std::max(0, las.front().aread); c < ncontigs && c <= las.back().aread; c++)
-        for (int64_t j = ptr[(size_t)c]; j < ptr[(size_t)c + 1]; j++) regions.push_back(dh_region{c, iv[(size_t)(2 * j)], iv[(size_t)(2 * j + 1)]});
+        for (int64_t j = ptr[(size_t)c]; j < ptr[(size_t)c + 1]; j++) {
+            regions.push_back(dh_region{c, iv[(size_t)(2 * j)], iv[(size_t)(2 * j + 1)]});
+            region_interval.push_back(j);
+        }
     must(dh_ctx_create(0, nullptr, into(ctx)));
     RegionResult res;
     must(dh_la_validate_regions(ctx.get(), las.data(), n, dh_dazz_offsets(da.get()), ncontigs, regions.data(), (int32_t)regions.size(), context, window,
@@ -202,7 +231,16 @@ int tool_validate_regions(const Args &args)
                regions[r].contig + first_contig, regions[r].begin, regions[r].end, regions[r].contig + first_contig, rep[r].ctx_begin,
                rep[r].ctx_end, rep[r].is_valid ? "true" : "false", rep[r].num_spanning_reads);
         for (int64_t k = span_off[r]; k < span_off[r + 1]; k++) printf("%s%d", k > span_off[r] ? "," : "", span_ids[k] + first_read);
-        printf("],\"weakCoverageMaskBps\":%d}\n", rep[r].weak_bp);
+        printf("],\"weakCoverageMaskBps\":%d", rep[r].weak_bp);
+        const int64_t j = region_interval[r];
+        if (has_contigs && contig_ids[(size_t)(2 * j)] > 0) {  // the ids as stored (:373-377)
+            printf(",\"contigIds\":[%lld,%lld],\"consensusReadIds\":[", (long long)contig_ids[(size_t)(2 * j)], (long long)contig_ids[(size_t)(2 * j + 1)]);
+            if (has_reads)
+                for (int64_t k = read_off[(size_t)j]; k < read_off[(size_t)j + 1]; k++)
+                    printf("%s%lld", k > read_off[(size_t)j] ? "," : "", (long long)read_ids[(size_t)k]);
+            printf("]");
+        }
+        printf("}\n");
     }
     if (!out_mask.empty())
         must(write_mask(pos[0], out_mask, ncontigs, dh_region_result_mask_ptr(res.get()), dh_region_result_mask_iv(res.get()),
