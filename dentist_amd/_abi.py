@@ -177,6 +177,7 @@ _PROTOTYPES = {
     "dh_join_hit_capacity": (i64, [vp, vp, i32, i32, f64, i64]),
     "dh_align_db": (cint, [vp, vp, vp, P(AlignOpts), i32, P(vp)]),
     "dh_seed_candidates": (cint, [vp, vp, vp, P(AlignOpts), vp, vp, vp]),
+    "dh_extend_candidates": (cint, [vp, vp, vp, P(AlignOpts), vp, vp, i32, P(vp), P(vp)]),
     "dh_set_near_best": (None, [i32]),
     "dh_ctx_set_near_best": (cint, [vp, i32]),
     "dh_align_db_block": (cint, [vp, vp, vp, i32, i32, P(AlignOpts), i32, P(vp)]),

@@ -215,6 +215,20 @@ def seed_candidates(ctx, A, B, opts):
     return cand, ncand, nhits
 
 
+def extend_candidates(ctx, A, B, opts, cand, ncand, sort=False, transposed=False):
+    n = 2 * int(lib().dh_db_nreads(B._h))
+    cand = np.ascontiguousarray(cand, dtype=SEED_CAND_DTYPE)
+    ncand = np.ascontiguousarray(ncand, dtype=np.int32)
+    if cand.size != n * int(opts.max_cand) or ncand.size != n:
+        raise DhError(-1, "extend_candidates: cand is [2 n(B), max_cand], ncand [2 n(B)]")
+    h, h2 = ctypes.c_void_p(), ctypes.c_void_p()
+    _check(lib().dh_extend_candidates(ctx._h, A._h, B._h, ctypes.byref(opts), cand.ctypes.data, ncand.ctypes.data, int(sort),
+                                      ctypes.byref(h), ctypes.byref(h2) if transposed else None))
+    if transposed:
+        return _take_la_set(h)[:2], _take_la_set(h2)[:2]
+    return _take_la_set(h)[:2]
+
+
 def merge_las(handles):
     """LAmerge of in-memory block results (handles from align_db_block(raw=True), consumed)."""
     arr = (ctypes.c_void_p * len(handles))(*[h.value for h in handles])

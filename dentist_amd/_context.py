@@ -83,6 +83,12 @@ class Context(Owner):
         takes them (what lies behind them is not defined)."""
         return _align.seed_candidates(self, A, B, opts)
 
+    def extend_candidates(self, A, B, opts, cand, ncand, sort=False, transposed=False):
+        """dh_extend_candidates: the extension stage of align_db alone on the caller's candidates (cand[nitems, max_cand]
+        SEED_CAND_DTYPE, ncand[nitems], item = 2 * read + strand), taken as they stand.  Returns (records, trace u16) in item
+        and slot order (sort=True: LAsort order); transposed=True: ((records, trace), (transposed records, trace))."""
+        return _align.extend_candidates(self, A, B, opts, cand, ncand, sort, transposed)
+
     def map_reads(self, A, B, opts, popts, first=0, count=None, repeat_mask=None, sorted=True, candidates=False,
                   trace_on_device=False):
         """dh_map_reads: the mapping pass (chain flags as with select_best) with the six `collect` filters

@@ -29,7 +29,7 @@ extern "C" int dh_align_db(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_align_opts 
 
 static int align_range(dh_ctx *ctx, dh_db *A, dh_db *B, int32_t first, int32_t count, const dh_align_opts *opts,
                        int32_t want_best, int32_t want_sorted, dh_la_set **out, const ChunkHook *hook = nullptr,
-                       dh_la_set **out_tr = nullptr, const SeedDump *dump = nullptr);
+                       dh_la_set **out_tr = nullptr, const SeedDump *dump = nullptr, const CandPlant *plant = nullptr);
 
 // `damapper <ref> <reads>.<block>` (snakemake/Snakefile:1143-1170): the reads [first, first + count)
 // of B against all of A; read ids in the records are those of the whole DB, as in a block's .las
@@ -121,6 +121,15 @@ extern "C" int dh_seed_candidates(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_alig
     return align_range(ctx, A, B, 0, B->n, opts, 0, 1, &none, nullptr, nullptr, &dump);
 }
 
+// the extension stage of dh_align_db(ctx, A, B, opts) alone: align_range with the caller's candidates in seed_chunk's place
+extern "C" int dh_extend_candidates(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_align_opts *opts, const dh_seed_cand *cand,
+                                    const int32_t *ncand, int32_t want_sorted, dh_la_set **out, dh_la_set **out_transposed)
+{
+    if (!B || !cand || !ncand) return fail(DH_EINVAL, "dh_extend_candidates: NULL argument");
+    const CandPlant plant{cand, ncand};
+    return align_range(ctx, A, B, 0, B->n, opts, 0, want_sorted ? 1 : 0, out, nullptr, out_transposed, nullptr, &plant);
+}
+
 // ---- align_range: the reads [first, first + count) of B against A, chunk by chunk.  Every chunk runs the same stages on
 // ctx->stream -- the plan of its mapping join, its derived copies, the seeds, the extension, the gather -- and AlignRun
 // holds what crosses them for one call.
@@ -150,6 +159,31 @@ static int check_align_args(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_align_opts
     if (o.skip_self == 3 && (o.algo != 1 || o.strands != 1 || hook || out_tr))
         return fail(DH_EINVAL, "skip_self 3 (a read against itself, datander) is defined for DH-2 (algo 1) on the forward strand (strands 1)");
     if (o.kmer_mod < 1 || o.kmer_mod > 64) return fail(DH_EINVAL, "kmer_mod must be in [1, 64]");
+    return DH_OK;
+}
+
+// dh_extend_candidates: nothing a planted candidate says may take a kernel outside its sequences, or outside what the seed
+// stage could have said under the same options (all items of the call, on the host, before anything is launched)
+static int check_plant(const dh_db *A, const dh_db *B, const dh_align_opts &o, const CandPlant &p)
+{
+    for (int64_t it = 0; it < 2ll * B->n; it++) {
+        const int32_t n = p.ncand[it], read = (int32_t)(it >> 1);
+        if (n < 0 || n > o.max_cand) return fail(DH_EINVAL, "dh_extend_candidates: ncand outside [0, max_cand]");
+        if (n > 0 && !(o.strands & (1 << (it & 1)))) return fail(DH_EINVAL, "dh_extend_candidates: candidates on a strand that opts->strands leaves out");
+        const int64_t blen = B->h_off[(size_t)read + 1] - B->h_off[(size_t)read];
+        const dh_seed_cand *row = p.cand + it * o.max_cand;
+        for (int32_t c = 0; c < n; c++) {
+            const dh_seed_cand &q = row[c];
+            if (q.aseq < 0 || q.aseq >= A->n) return fail(DH_EINVAL, "dh_extend_candidates: aseq outside A");
+            const int64_t alen = A->h_off[(size_t)q.aseq + 1] - A->h_off[(size_t)q.aseq];
+            if (q.apos < 0 || q.apos > alen) return fail(DH_EINVAL, "dh_extend_candidates: apos outside its sequence");
+            if (q.bpos < 0 || q.bpos > blen) return fail(DH_EINVAL, "dh_extend_candidates: bpos outside its read");
+            if ((o.skip_self == 1 || o.skip_self == 2) && q.aseq == read)
+                return fail(DH_EINVAL, "dh_extend_candidates: skip_self 1 and 2 take no candidate of a read on itself");
+            if (o.skip_self == 3 && (q.aseq != read || q.apos <= q.bpos))
+                return fail(DH_EINVAL, "dh_extend_candidates: skip_self 3 takes candidates of a read on itself with apos > bpos");
+        }
+    }
     return DH_OK;
 }
 
@@ -239,11 +273,13 @@ static int dump_seeds(AlignRun &r, const AlignChunk &c, const SeedDump &d)
 
 static int align_range(dh_ctx *ctx, dh_db *A, dh_db *B, int32_t first, int32_t count, const dh_align_opts *opts,
                        int32_t want_best, int32_t want_sorted, dh_la_set **out, const ChunkHook *hook, dh_la_set **out_tr,
-                       const SeedDump *dump)
+                       const SeedDump *dump, const CandPlant *plant)
 {
     const double wall0 = now_ms() * 1e3;
     double w_a = now_ms();
     if (int rc = check_align_args(ctx, A, B, opts, out, hook, out_tr)) return rc;
+    if (plant)
+        if (int rc = check_plant(A, B, *opts, *plant)) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     AlignRun r(ctx, A, B, *opts, first, count, want_best, want_sorted, hook);
     const dh_align_opts &o = r.o;
@@ -291,10 +327,11 @@ static int align_range(dh_ctx *ctx, dh_db *A, dh_db *B, int32_t first, int32_t c
         c.item0 = item0;
         c.ni = (int32_t)std::min<int64_t>(r.cn, r.item_end - item0);
         r.w_c = now_ms();
-        if (int rc = plan_mj_chunk(r, c)) return rc;
+        if (!plant)  // (planted candidates: no join of the chunk is planned, no k-mer is looked up)
+            if (int rc = plan_mj_chunk(r, c)) return rc;
         if (int rc = copy_chunk(r, c)) return rc;
         SeedRedo redo = SEED_DONE;
-        if (int rc = seed_chunk(r, c, &redo)) return rc;
+        if (int rc = plant ? plant_chunk(r, c, *plant) : seed_chunk(r, c, &redo)) return rc;
         if (redo != SEED_DONE) continue;  // the same chunk again (SeedRedo says why)
         r.lap(1);
         if (dump) {  // dh_seed_candidates: the chunk ends here

@@ -1,6 +1,6 @@
 // dh_align.h -- what the host files of the alignment pipeline share (dh_align.cpp, dh_align_prepare.cpp, dh_align_join.cpp,
 // dh_align_seed.cpp, dh_align_extend.cpp): the state of a call and of a chunk, and the stages align_range runs.  Lives:
-// ChunkHook and SeedDump are the caller's, for one call; AlignRun and JoinPlan are made by align_range and live for that
+// ChunkHook, SeedDump and CandPlant are the caller's, for one call; AlignRun and JoinPlan are made by align_range and live for that
 // call; Tasks is a member of AlignRun and is joined before the result is handed out or can move; AlignChunk and its
 // ChunkCopies are made anew for every pass of the chunk loop (a chunk that runs again starts from an empty one).  What one
 // file alone uses stays in that file.
@@ -26,6 +26,13 @@ typedef std::function<void(dh_la *, int64_t, int64_t, int64_t)> ChunkHook;
 struct SeedDump {
     dh_seed_cand *cand;
     int32_t *ncand, *nhits;
+};
+
+// dh_extend_candidates: the caller's candidates (row 0 = the first item of the call); with it a chunk gets its seeds from
+// these rows and seed_chunk does not run
+struct CandPlant {
+    const dh_seed_cand *cand;
+    const int32_t *ncand;
 };
 
 // derived copies (reverse complement, 2-bit packed forward / reverse) of the reads [r0, r1) of B in
@@ -197,6 +204,7 @@ int copy_chunk(AlignRun &r, AlignChunk &c);
 int plan_seeds(AlignRun &r);
 int plan_mj_chunk(AlignRun &r, AlignChunk &c);
 int seed_chunk(AlignRun &r, AlignChunk &c, SeedRedo *redo);
+int plant_chunk(AlignRun &r, AlignChunk &c, const CandPlant &plant);
 // dh_align_extend.cpp
 int extend_chunk(AlignRun &r, AlignChunk &c);
 int gather_chunk(AlignRun &r, AlignChunk &c);

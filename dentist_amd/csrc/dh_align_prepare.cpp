@@ -138,8 +138,19 @@ int alloc_scratch(AlignRun &r)
     if (const char *e = getenv("DH_WAVE_SLOTS_PER_CU")) slots_per_cu = std::max(4, atoi(e)) & ~3;
     // trace-node pool of one alignment slot.  k_wave2: every lane of the group owns a stretch (a lane
     // crosses each boundary of either grid at most once per diagonal it serves; twice that is the
-    // capacity, an overflow is reported); k_wave: one shared pool
-    r.poolcap = r.dual ? (64 / r.per_wave) * (4 * nbmax + 8) : 96 * nbmax;
+    // capacity, an overflow is reported); k_wave: one shared pool.  At the END of a sequence that is a boundary itself (the
+    // start of A' always is one for the reverse extension) a diagonal that cannot advance gets a new cell from its lower
+    // neighbour on every level and crosses that boundary again: one more node per level, grid and extension for as long as
+    // the wave outlives its best point -- about (xdrop + 64) / pen + 2 levels, never more than dmax.  Sequences of a few tile
+    // lengths (nbmax 3 or 4) overflowed 4 nbmax + 8 that way, symmetric calls first (two grids).  Like 4 nbmax + 8 this is an
+    // EMPIRICAL allowance, sized on node counts of constructed cases (LABNOTES 32: at most a third of it was used), not a
+    // proven bound: the best point can still move while a diagonal sits at the end.  A lane that runs out writes nothing
+    // past its stretch and the call reports DH_EOVERFLOW.  (64-bit: xdrop and dmax are the caller's; the stretch of a lane
+    // is capped at 2^20 nodes.)
+    const int64_t end_levels = std::min<int64_t>((std::max<int64_t>(o.xdrop, 0) + 64) / o.pen + 2, std::max<int64_t>(o.dmax, 0));
+    const int64_t end_nodes = 2 * (o.skip_self == 2 ? 2 : 1) * end_levels;
+    const int64_t lane_nodes = std::min<int64_t>(4ll * nbmax + 8 + end_nodes, 1ll << 20);
+    r.poolcap = r.dual ? (int32_t)((64 / r.per_wave) * lane_nodes) : 96 * nbmax;
     r.nslots = r.tiled ? 4 : (int32_t)std::min<int64_t>((int64_t)ctx->ncu * slots_per_cu,
                                                         (std::max<int64_t>(nitems_total, 4) + 3) & ~3ll);
     // DH-2: one alignment per lane; wavefronts resident = CUs x waves per CU, no more than the items need

@@ -444,6 +444,18 @@ static int run_hbm_pass(AlignRun &r, AlignChunk &c, const SeedSource &src, const
     return DH_OK;
 }
 
+// dh_extend_candidates: the chunk's seeds are the caller's rows of its items -- the set-up of seed_chunk, then three copies
+int plant_chunk(AlignRun &r, AlignChunk &c, const CandPlant &plant)
+{
+    if (int rc = shift_bases(r, c)) return rc;
+    const size_t at = (size_t)(c.item0 - r.item_first), ni = (size_t)c.ni;
+    HIPCHK(hipMemcpyAsync(r.d_cand, plant.cand + at * r.o.max_cand, sizeof(DhCand) * ni * r.o.max_cand, hipMemcpyHostToDevice, r.st));
+    HIPCHK(hipMemcpyAsync(r.d_ncand, plant.ncand + at, sizeof(int32_t) * ni, hipMemcpyHostToDevice, r.st));
+    HIPCHK(hipMemsetAsync(r.d_nhits, 0, sizeof(int32_t) * ni, r.st));
+    HIPCHK(hipStreamSynchronize(r.st));
+    return DH_OK;
+}
+
 // The seeds of a chunk: the first tier of the seed filter (fed by the mapping join, the pile-up join or the directory),
 // then the reads that overflowed it -- further tiers of the join path, the rest staged in HBM.  *redo: the chunk has to
 // run again (the join's hit pool ran out, a capacity of the join was exceeded, or the directory path doubled its cap).

@@ -19,7 +19,7 @@ int dh_fail(int code, const std::string &msg)
 #define fail dh_fail
 
 extern "C" const char *dh_last_error(void) { return g_err.c_str(); }
-extern "C" int32_t dh_abi_version(void) { return 4; }  // 4: dh_process_opts.max_partners, .min_relative_score_ppm (64 bytes); 3: dh_align_opts.algo
+extern "C" int32_t dh_abi_version(void) { return 5; }  // 5: dh_extend_candidates (no struct changed); 4: dh_process_opts.max_partners, .min_relative_score_ppm (64 bytes); 3: dh_align_opts.algo
 
 // ------------------------------------------------------------------------------------ context
 

@@ -412,7 +412,8 @@ __device__ int32_t emit_trace(int lane, int stride, int32_t ts, int32_t res, int
     int32_t gm = (gs - res) % ts;
     gm = gm < 0 ? gm + ts : gm;
     const int32_t seedb = (gm == 0 && gs > gbeg && gs < gend) ? 1 : 0;
-    const int32_t npairs = nrv + seedb + nfv + 1;
+    // (a zero-length alignment -- two empty extensions, kept at min_len 0 -- has no pair at all, as in the oracle)
+    const int32_t npairs = nrv + seedb + nfv + (gend > gbeg ? 1 : 0);
     for (int32_t e = lane; e < npairs; e += stride) {
         int32_t po[2], pD[2];
 #pragma unroll

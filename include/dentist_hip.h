@@ -31,7 +31,7 @@ extern "C" {
 
 const char *dh_last_error(void);
 /* library / ABI version, bumped on any struct change (4: dh_process_opts is 64 bytes -- max_partners,
- * min_relative_score_ppm; callers check it before passing structs) */
+ * min_relative_score_ppm; 5: dh_extend_candidates, no struct changed; callers check it before passing structs) */
 int32_t dh_abi_version(void);
 
 /* ---- context: one per process == one per GPU (torch.distributed launches one rank per GPU) */
@@ -213,6 +213,18 @@ typedef struct { int32_t score, aseq, apos, bpos; } dh_seed_cand;   /* == DhCand
  * cumulative statistics do not count the call.  (Tests: which tier or join disagrees on which item.) */
 int dh_seed_candidates(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_align_opts *opts,
                        dh_seed_cand *cand, int32_t *ncand, int32_t *nhits);
+/* The extension stage of dh_align_db alone, the mirror of dh_seed_candidates: the call runs as dh_align_db does, but every
+ * item (2 * read + strand of B) extends the caller's candidates -- cand[item * opts->max_cand + c], c < ncand[item], taken
+ * as they stand -- where the seed stage would have produced them (symmetric mode, skip_self 2: the candidates of an item
+ * grouped by aseq, every unordered pair in one item only, as the seed stage leaves them).  No k-mer is looked up; the
+ * result does not depend on what A and B share.  want_sorted 0: records in item and slot order (symmetric mode: slots are
+ * claimed in arrival order); 1: LAsort order.  out_transposed may be NULL; it is accepted under the conditions of
+ * dh_align_db_transposed.  Checked on the host before anything is launched, DH_EINVAL otherwise: 0 <= ncand <= max_cand,
+ * 0 <= aseq < n(A), 0 <= apos <= alen, 0 <= bpos <= blen; ncand = 0 for the items of a strand that opts->strands leaves out;
+ * skip_self 1 and 2: aseq != read; skip_self 3: aseq == read and apos > bpos.  dh_get_align_stats then gives alignments, wave_cells, las, overflow_items and wave_launches of the call
+ * (hits 0, cands the sum of ncand).  (Tests: which kernel disagrees on which candidate.) */
+int dh_extend_candidates(dh_ctx *ctx, dh_db *A, dh_db *B, const dh_align_opts *opts, const dh_seed_cand *cand,
+                         const int32_t *ncand, int32_t want_sorted, dh_la_set **out, dh_la_set **out_transposed);
 /* select_best: damapper's chains.  The LAs of a read on one contig and strand that follow each other (gaps <= 10 kb,
  * gap difference <= 6 kb: a long indel splits a mapping into collinear LAs) form a chain: START (0x4) on its first
  * LA, NEXT (0x8) on the others, BEST (0x10) on the LAs of the chain that no higher-scoring chain of the strand covers

@@ -1016,6 +1016,104 @@ static int la_accept(const oz_la *la, const oz_opts *o)
     return (int64_t)2 * la->diffs * 1000000 <= (int64_t)o->max_err_ppm * (al + bl);
 }
 
+/* The extension of one item's candidates: b = read r of B on `strand` (blen bases), cands[0..nc) taken as they stand.
+ * The candidate loop with its finished regions (at most 64 attempts), the acceptance, the symmetric and the transposed
+ * second record.  att (optional): one row of OZ_ATT_FIELDS values per candidate slot, see oz_extend_candidates. */
+static void extend_cands(const oz_db *A, const uint8_t *b, int32_t blen, int32_t r, int strand, const oz_opts *o,
+                         const oz_cand *cands, int nc, const uint8_t *pf, oz_la_set *out, oz_la_set *out2, int64_t *stats,
+                         uint16_t *trace, uint16_t *trace2, int64_t *att)
+{
+    region done[64];
+    int nd = 0, nacc = 0;
+    /* symmetric mode: max_la is only a capacity (a record may also arrive from its partner) */
+    for (int c = 0; c < nc && (o->skip_self == 2 || nacc < o->max_la) && nd < 64; c++) {
+        const oz_cand *cd = &cands[c];
+        const int32_t sd = cd->apos - cd->bpos;
+        int covered = 0;
+        for (int t = 0; t < nd; t++)
+            if (done[t].aseq == cd->aseq && cd->apos >= done[t].abpos &&
+                cd->apos < done[t].aepos && cd->bpos >= done[t].bbpos &&
+                cd->bpos < done[t].bepos && sd >= done[t].dlo - 64 && sd <= done[t].dhi + 64)
+                covered = 1;
+        if (covered) {
+            if (att) att[(int64_t)c * OZ_ATT_FIELDS] = 1;
+            continue;
+        }
+        const uint8_t *a = A->bases + A->off[cd->aseq];
+        const int32_t alen = (int32_t)(A->off[cd->aseq + 1] - A->off[cd->aseq]);
+        oz_la la, la2;
+        memset(&la, 0, sizeof(la));
+        memset(&la2, 0, sizeof(la2));
+        int32_t dlo, dhi;
+        const int sym = o->skip_self == 2, tiled = o->algo == 1;
+        const int64_t cells0 = stats[3];
+        /* DH-1 derives the transposed record from the same path (second trace grid); DH-2 aligns the
+         * transposed pair on its own, below, once the first record is in */
+        local_align2(a, alen, b, blen, cd->apos, cd->bpos, o, &la, trace, sym && !tiled ? &la2 : NULL,
+                     sym && !tiled ? trace2 : NULL, strand, &dlo, &dhi, &stats[3]);
+        stats[2]++;
+        done[nd].aseq = cd->aseq;
+        done[nd].abpos = la.abpos;
+        done[nd].aepos = la.aepos;
+        done[nd].bbpos = la.bbpos;
+        done[nd].bepos = la.bepos;
+        done[nd].dlo = dlo;
+        done[nd].dhi = dhi;
+        nd++;
+        const int ok = la_accept(&la, o);
+        int64_t *row = att ? att + (int64_t)c * OZ_ATT_FIELDS : NULL;
+        if (row) {
+            row[0] = ok ? 3 : 2;
+            row[1] = la.abpos;
+            row[2] = la.aepos;
+            row[3] = la.bbpos;
+            row[4] = la.bepos;
+            row[5] = la.diffs;
+            row[6] = dlo;
+            row[7] = dhi;
+            row[8] = stats[3] - cells0;
+        }
+        if (!ok) continue;
+        la.aread = cd->aseq;
+        la.bread = r;
+        la.flags = strand ? OZ_FLAG_COMP : 0;
+        if (!sym || rec_wanted(pf, cd->aseq, r)) la_set_push(out, &la, trace);
+        if ((sym || out2) && tiled && (!sym || rec_wanted(pf, r, cd->aseq))) {
+            /* DH-2, symmetric (or the transposed file of a mapping): the record (b, a) is the tiled alignment of the transposed pair through the
+             * same seed -- A'' = the read behind B on its forward strand (the trace grid of that record),
+             * B'' = the A read, complemented when B is (then both axes are mirrored: the seed point
+             * (as, bs) becomes (blen - bs, alen - as)).  It is accepted on its own length and error. */
+            uint8_t *a2 = (uint8_t *)malloc((size_t)blen + 1), *b2 = (uint8_t *)malloc((size_t)alen + 1);
+            if (strand) {
+                oz_revcomp(b, blen, a2);
+                oz_revcomp(a, alen, b2);
+            } else {
+                memcpy(a2, b, (size_t)blen);
+                memcpy(b2, a, (size_t)alen);
+            }
+            int32_t d2lo, d2hi;
+            local_align2(a2, blen, b2, alen, strand ? blen - cd->bpos : cd->bpos, strand ? alen - cd->apos : cd->apos,
+                         o, &la2, trace2, NULL, NULL, 0, &d2lo, &d2hi, &stats[3]);
+            free(a2);
+            free(b2);
+            if (row) row[8] = stats[3] - cells0; /* (the cells of the transposed pair belong to the attempt) */
+            if (la_accept(&la2, o)) {
+                la2.aread = r;
+                la2.bread = cd->aseq;
+                la2.flags = la.flags;
+                la_set_push(sym ? out : out2, &la2, trace2);
+            }
+        } else if (sym && !tiled) { /* DH-1: the transposed record of the same alignment, A and B swapped.  (DH-2 with pflags
+                                     * and the record (b, a) not wanted: nothing -- this branch used to emit a zeroed la2) */
+            la2.aread = r;
+            la2.bread = cd->aseq;
+            la2.flags = la.flags;
+            la_set_push(out, &la2, trace2);
+        }
+        nacc++;
+    }
+}
+
 /* out2 (optional, DH-2 and A != B only): the records of the transposed pairs -- `damapper -C`'s second file */
 static void align_read(const oz_index *ix, const oz_db *A, const oz_db *B, int32_t r,
                        const oz_opts *o, oz_la_set *out, oz_la_set *out2, int64_t *stats, oz_cand *cands,
@@ -1040,77 +1138,63 @@ static void align_read(const oz_index *ix, const oz_db *A, const oz_db *B, int32
         free(tmpm);
         stats[0] += nh;
         stats[1] += nc;
-        region done[64];
-        int nd = 0, nacc = 0;
-        /* symmetric mode: max_la is only a capacity (a record may also arrive from its partner) */
-        for (int c = 0; c < nc && (o->skip_self == 2 || nacc < o->max_la) && nd < 64; c++) {
-            const oz_cand *cd = &cands[c];
-            const int32_t sd = cd->apos - cd->bpos;
-            int covered = 0;
-            for (int t = 0; t < nd; t++)
-                if (done[t].aseq == cd->aseq && cd->apos >= done[t].abpos &&
-                    cd->apos < done[t].aepos && cd->bpos >= done[t].bbpos &&
-                    cd->bpos < done[t].bepos && sd >= done[t].dlo - 64 && sd <= done[t].dhi + 64)
-                    covered = 1;
-            if (covered) continue;
-            const uint8_t *a = A->bases + A->off[cd->aseq];
-            const int32_t alen = (int32_t)(A->off[cd->aseq + 1] - A->off[cd->aseq]);
-            oz_la la, la2;
-            memset(&la, 0, sizeof(la));
-            memset(&la2, 0, sizeof(la2));
-            int32_t dlo, dhi;
-            const int sym = o->skip_self == 2, tiled = o->algo == 1;
-            /* DH-1 derives the transposed record from the same path (second trace grid); DH-2 aligns the
-             * transposed pair on its own, below, once the first record is in */
-            local_align2(a, alen, b, blen, cd->apos, cd->bpos, o, &la, trace, sym && !tiled ? &la2 : NULL,
-                         sym && !tiled ? trace2 : NULL, strand, &dlo, &dhi, &stats[3]);
-            stats[2]++;
-            done[nd].aseq = cd->aseq;
-            done[nd].abpos = la.abpos;
-            done[nd].aepos = la.aepos;
-            done[nd].bbpos = la.bbpos;
-            done[nd].bepos = la.bepos;
-            done[nd].dlo = dlo;
-            done[nd].dhi = dhi;
-            nd++;
-            if (!la_accept(&la, o)) continue;
-            la.aread = cd->aseq;
-            la.bread = r;
-            la.flags = strand ? OZ_FLAG_COMP : 0;
-            if (!sym || rec_wanted(pf, cd->aseq, r)) la_set_push(out, &la, trace);
-            if ((sym || out2) && tiled && (!sym || rec_wanted(pf, r, cd->aseq))) {
-                /* DH-2, symmetric (or the transposed file of a mapping): the record (b, a) is the tiled alignment of the transposed pair through the
-                 * same seed -- A'' = the read behind B on its forward strand (the trace grid of that record),
-                 * B'' = the A read, complemented when B is (then both axes are mirrored: the seed point
-                 * (as, bs) becomes (blen - bs, alen - as)).  It is accepted on its own length and error. */
-                uint8_t *a2 = (uint8_t *)malloc((size_t)blen + 1), *b2 = (uint8_t *)malloc((size_t)alen + 1);
-                if (strand) {
-                    oz_revcomp(b, blen, a2);
-                    oz_revcomp(a, alen, b2);
-                } else {
-                    memcpy(a2, b, (size_t)blen);
-                    memcpy(b2, a, (size_t)alen);
-                }
-                int32_t d2lo, d2hi;
-                local_align2(a2, blen, b2, alen, strand ? blen - cd->bpos : cd->bpos, strand ? alen - cd->apos : cd->apos,
-                             o, &la2, trace2, NULL, NULL, 0, &d2lo, &d2hi, &stats[3]);
-                free(a2);
-                free(b2);
-                if (la_accept(&la2, o)) {
-                    la2.aread = r;
-                    la2.bread = cd->aseq;
-                    la2.flags = la.flags;
-                    la_set_push(sym ? out : out2, &la2, trace2);
-                }
-            } else if (sym) { /* the transposed record of the same alignment: A and B swapped */
-                la2.aread = r;
-                la2.bread = cd->aseq;
-                la2.flags = la.flags;
-                la_set_push(out, &la2, trace2);
+        extend_cands(A, b, blen, r, strand, o, cands, nc, pf, out, out2, stats, trace, trace2, NULL);
+    }
+}
+
+static int align_mode_ok(const oz_opts *o, const oz_la_set *out2)
+{
+    if (out2 && (o->algo != 1 || o->skip_self == 2)) return 0; /* the transposed file is defined for DH-2 mappings */
+    if (o->skip_self == 3 && (o->algo != 1 || o->strands != 1)) return 0; /* tandem: DH-2, forward strand (A and B: the same DB) */
+    return 1;
+}
+
+/* The extension stage alone: item = 2 * read + strand of B, cand[item * max_cand + c] for c < ncand[item] as the
+ * candidates of that item, in that order.  Items of a strand that opts->strands leaves out are passed over.  Records
+ * arrive in item and candidate order.  attempts (optional): int64[nitems * max_cand][OZ_ATT_FIELDS], zeroed here. */
+int oz_extend_candidates(const oz_db *A, const oz_db *B, const oz_opts *o, const oz_cand *cand, const int32_t *ncand,
+                         int nthreads, oz_la_set *out, oz_la_set *out2, int64_t *stats, int64_t *attempts)
+{
+    (void)nthreads; /* one thread: the stage is run on small constructed inputs */
+    if (!align_mode_ok(o, out2)) return -1;
+    int32_t max_blen = 0, max_alen = 0;
+    for (int32_t r = 0; r < B->n; r++) {
+        int32_t l = (int32_t)(B->off[r + 1] - B->off[r]);
+        if (l > max_blen) max_blen = l;
+    }
+    for (int32_t s = 0; s < A->n; s++) {
+        int32_t l = (int32_t)(A->off[s + 1] - A->off[s]);
+        if (l > max_alen) max_alen = l;
+    }
+    const int32_t mlen = max_alen > max_blen ? max_alen : max_blen;
+    uint8_t *rc = (uint8_t *)malloc((size_t)max_blen + 1);
+    uint16_t *trace = (uint16_t *)malloc((size_t)(2 * (mlen / o->tspace + 4)) * sizeof(uint16_t));
+    uint16_t *trace2 = (uint16_t *)malloc((size_t)(2 * (mlen / o->tspace + 4)) * sizeof(uint16_t));
+    int64_t st[4] = {0, 0, 0, 0};
+    if (attempts) memset(attempts, 0, (size_t)2 * (size_t)B->n * (size_t)o->max_cand * OZ_ATT_FIELDS * sizeof(int64_t));
+    const uint8_t *pf = o->skip_self == 2 && o->algo == 1 ? A->pflags : NULL;
+    for (int32_t r = 0; r < B->n; r++) {
+        const uint8_t *bf = B->bases + B->off[r];
+        const int32_t blen = (int32_t)(B->off[r + 1] - B->off[r]);
+        for (int strand = 0; strand < 2; strand++) {
+            const int64_t item = 2 * (int64_t)r + strand;
+            st[1] += ncand[item];
+            if (!(o->strands & (1 << strand))) continue;
+            const uint8_t *b = bf;
+            if (strand) {
+                oz_revcomp(bf, blen, rc);
+                b = rc;
             }
-            nacc++;
+            extend_cands(A, b, blen, r, strand, o, cand + item * o->max_cand, ncand[item], pf, out, out2, st, trace,
+                         trace2, attempts ? attempts + item * o->max_cand * OZ_ATT_FIELDS : NULL);
         }
     }
+    free(rc);
+    free(trace);
+    free(trace2);
+    if (stats)
+        for (int q = 0; q < 4; q++) stats[q] = st[q];
+    return 0;
 }
 
 int oz_align_db(const oz_db *A, const oz_db *B, const oz_opts *o, int nthreads, oz_la_set *out,
@@ -1122,8 +1206,7 @@ int oz_align_db(const oz_db *A, const oz_db *B, const oz_opts *o, int nthreads, 
 int oz_align_db2(const oz_db *A, const oz_db *B, const oz_opts *o, int nthreads, oz_la_set *out, oz_la_set *out2,
                  int64_t *stats)
 {
-    if (out2 && (o->algo != 1 || o->skip_self == 2)) return -1; /* the transposed file is defined for DH-2 mappings */
-    if (o->skip_self == 3 && (o->algo != 1 || o->strands != 1)) return -1; /* tandem: DH-2, forward strand (A and B: the same DB) */
+    if (!align_mode_ok(o, out2)) return -1;
     int32_t max_blen = 0, max_alen = 0;
     for (int32_t r = 0; r < B->n; r++) {
         int32_t l = (int32_t)(B->off[r + 1] - B->off[r]);

@@ -149,6 +149,15 @@ int oz_align_db(const oz_db *A, const oz_db *B, const oz_opts *o, int nthreads, 
 int oz_align_db2(const oz_db *A, const oz_db *B, const oz_opts *o, int nthreads, oz_la_set *out, oz_la_set *out2,
                  int64_t *stats);
 
+/* The extension stage of oz_align_db2 alone, on candidates the caller gives: item = 2 * read + strand of B,
+ * cand[item * max_cand + c], c < ncand[item], taken as they stand (nothing is sorted or grouped again).  Records in item
+ * and candidate order; stats[0] = 0, [1] = sum of ncand, [2] = attempts, [3] = cells.  attempts (may be NULL): one row of
+ * OZ_ATT_FIELDS int64 per candidate slot -- state (0 not reached, 1 skipped as covered, 2 aligned and rejected,
+ * 3 accepted), the raw box abpos, aepos, bbpos, bepos, diffs, the region's dlo, dhi, the cells of the attempt. */
+#define OZ_ATT_FIELDS 9
+int oz_extend_candidates(const oz_db *A, const oz_db *B, const oz_opts *o, const oz_cand *cand, const int32_t *ncand,
+                         int nthreads, oz_la_set *out, oz_la_set *out2, int64_t *stats, int64_t *attempts);
+
 /* damapper-style per-read selection: sets START/BEST flags (dazzler.d:1728-1758 consumer) */
 void oz_select_best(oz_la_set *s);
 void oz_set_near_best(int32_t ppm); /* damapper -n as parts per million, 0 = keep every chain */

@@ -117,7 +117,8 @@ def _take(ls):
     if n:
         buf = ctypes.string_at(ls.la, n * ctypes.sizeof(La))
         las = np.frombuffer(buf, dtype=LA_DTYPE).copy()
-        trace = np.ctypeslib.as_array(ls.trace, shape=(max(tn, 1),))[:tn].copy()
+        trace = (np.ctypeslib.as_array(ls.trace, shape=(tn,)).copy() if tn   # (records without a trace value: zero-length ones)
+                 else np.zeros(0, dtype=np.uint16))
     else:
         las = np.zeros(0, dtype=LA_DTYPE)
         trace = np.zeros(0, dtype=np.uint16)
@@ -425,3 +426,40 @@ def seed_candidates_all(A, B, opts, with_nhits=False):
     if with_nhits:
         return cand[:, :opts.max_cand], ncand, nhits
     return cand[:, :opts.max_cand], ncand
+
+
+# ---------------------------------------------------------------- the extension of given candidates
+ATT_FIELDS = ("state", "abpos", "aepos", "bbpos", "bepos", "diffs", "dlo", "dhi", "cells")
+ATT_NOT_REACHED, ATT_COVERED, ATT_REJECTED, ATT_ACCEPTED = 0, 1, 2, 3
+
+
+def extend_candidates(A, B, opts, cand, ncand, transposed=False, nthreads=1):
+    """oz_extend_candidates: the extension stage on the caller's candidates (cand[nitems, max_cand] CAND_DTYPE,
+    ncand[nitems], item = 2 * read + strand).  Returns (records, trace, stats[4], attempts[nitems, max_cand, 9]) with the
+    records in item and candidate order; transposed=True adds (records2, trace2) of the transposed file behind them."""
+    L = lib()
+    L.oz_extend_candidates.restype = ctypes.c_int
+    L.oz_extend_candidates.argtypes = [ctypes.POINTER(Db), ctypes.POINTER(Db), ctypes.POINTER(Opts), ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(LaSet), ctypes.POINTER(LaSet),
+                                       ctypes.c_void_p, ctypes.c_void_p]
+    nitems = 2 * B.n
+    cand = np.ascontiguousarray(cand, dtype=CAND_DTYPE).reshape(nitems, opts.max_cand)
+    ncand = np.ascontiguousarray(ncand, dtype=np.int32).reshape(nitems)
+    if ncand.min(initial=0) < 0 or ncand.max(initial=0) > opts.max_cand:
+        raise ValueError("ncand outside [0, max_cand]")
+    ls, ls2 = LaSet(), LaSet()
+    L.oz_la_set_init(ctypes.byref(ls))
+    L.oz_la_set_init(ctypes.byref(ls2))
+    stats = np.zeros(4, dtype=np.int64)
+    att = np.zeros((nitems, opts.max_cand, len(ATT_FIELDS)), dtype=np.int64)
+    da, dbb = _db(A), _db(B)
+    rc = L.oz_extend_candidates(ctypes.byref(da), ctypes.byref(dbb), ctypes.byref(opts), cand.ctypes.data, ncand.ctypes.data,
+                                nthreads, ctypes.byref(ls), ctypes.byref(ls2) if transposed else None, stats.ctypes.data,
+                                att.ctypes.data)
+    if rc != 0:
+        raise ValueError("oz_extend_candidates: options the oracle does not define (transposed file or tandem mode)")
+    las, trace = _take(ls)
+    if transposed:
+        return las, trace, stats, att, _take(ls2)
+    L.oz_la_set_free(ctypes.byref(ls2))
+    return las, trace, stats, att

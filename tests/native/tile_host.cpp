@@ -57,11 +57,12 @@ static void run_tile(Lane &l, const Params &P)
     tile_end<WB>(l, P, t);
 }
 
-extern "C" long dh_tile_host_align2(const uint8_t *abases, const int64_t *aoff, int32_t na, const uint8_t *bbases,
+// pflags (optional, symmetric mode): the per-sequence flags of DbView::pflags, one byte per sequence of A (= B)
+extern "C" long dh_tile_host_align3(const uint8_t *abases, const int64_t *aoff, int32_t na, const uint8_t *bbases,
                                     const int64_t *boff, int32_t nb, const DhOpts *o, const DhCand *cand,
                                     const int32_t *ncand, int32_t nbmax, DhLa *out_la, uint16_t *out_trace,
                                     long cap_trace, unsigned long long *counters, DhLa *out_la2, uint16_t *out_trace2,
-                                    long *n2)
+                                    long *n2, const uint8_t *pflags)
 {
     const int64_t PADW = 8;
     std::vector<uint8_t> arc, brc;
@@ -117,6 +118,8 @@ extern "C" long dh_tile_host_align2(const uint8_t *abases, const int64_t *aoff, 
     P.ncand = ncand;
     P.queue = &queue;
     P.book_min = 1;
+    P.tandem = o->skip_self == 3 ? 1 : 0;
+    P.pflags = o->skip_self == 2 ? pflags : nullptr;
     P.units = nullptr;
     P.nunits = nullptr;
     P.candoff = sym ? candoff.data() : nullptr;
@@ -196,6 +199,16 @@ extern "C" long dh_tile_host_align2(const uint8_t *abases, const int64_t *aoff, 
         *n2 = m;
     }
     return n;
+}
+
+extern "C" long dh_tile_host_align2(const uint8_t *abases, const int64_t *aoff, int32_t na, const uint8_t *bbases,
+                                    const int64_t *boff, int32_t nb, const DhOpts *o, const DhCand *cand,
+                                    const int32_t *ncand, int32_t nbmax, DhLa *out_la, uint16_t *out_trace,
+                                    long cap_trace, unsigned long long *counters, DhLa *out_la2, uint16_t *out_trace2,
+                                    long *n2)
+{
+    return dh_tile_host_align3(abases, aoff, na, bbases, boff, nb, o, cand, ncand, nbmax, out_la, out_trace, cap_trace, counters,
+                               out_la2, out_trace2, n2, nullptr);
 }
 
 extern "C" long dh_tile_host_align(const uint8_t *abases, const int64_t *aoff, int32_t na, const uint8_t *bbases,
